@@ -12,11 +12,16 @@ Weak scaling: per-GPU work is fixed as N grows; value = N * 1000 * steps / t.
 A step = one ``FlatIndex.search`` of 1000 queries (inputs already in HBM): query
 prep, the K7 sample pre-pass (1/16 of the tiles, running maxima only) that seeds the
 per-query threshold, the K7 fp16 MFMA scan, K8 merge + exact f64 rescore +
-certificate, the (normally empty) collect pass, and for N>1 the all-gather + merge. The CLIP
-ViT-B/32 leg (config 2) is reported beside it as ``clip`` when the encoder
-library is present.
+certificate, the (normally empty) collect pass, and for N>1 the all-gather + merge.
 
-Run: python bench.py [--gpus N --steps K --warmup W]; N>1 under
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line (metric,
+value, unit, ms_per_step, ...). ``--dump-outputs DIR`` also writes what the last timed step
+returned (``scores.npy``, ``rows.npy``); the inputs are seeded, so two builds can be compared
+output for output. ``--full`` adds every other measurement to the line: the one-search-in-flight
+run with the K7 roofline, the host-buffer and call-pattern legs, the ingest / index legs,
+config 5 (``fusion``), the CLIP ViT-B/32 leg (config 2, ``clip``) and the CPU baselines.
+
+Run: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]; N>1 under
 torch.distributed.run (one process per GPU, RCCL).
 """
 from __future__ import annotations
@@ -1041,6 +1046,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also measure everything else the result line can hold: the "
+                         "one-search-in-flight run with the K7 roofline, the host-buffer and call-pattern legs, "
+                         "ingest / index legs, config 5 (fusion), the CLIP leg and the CPU baselines "
+                         "(each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (scores.npy float32 [1000, 10], rows.npy "
+                         "float64 [1000, 10], global row ids) into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-clip", action="store_true")
     ap.add_argument("--no-fusion", action="store_true")
@@ -1059,7 +1072,8 @@ def main():
     if world != args.gpus:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE {world}", file=sys.stderr)
     dev = torch.device("cuda", local)
-    clip_streams = _early_streams(dev, 3) if rank == 0 and not args.no_clip else None
+    full = args.full
+    clip_streams = _early_streams(dev, 3) if full and rank == 0 and not args.no_clip else None
 
     from app.vector_store import FlatIndex
 
@@ -1096,14 +1110,16 @@ def main():
         with torch.cuda.stream(streams[i % nstreams]):
             return sharded.search_local(q, TOPK)
 
+    last = [None]  # what the latest step returned: (scores f32 [NQ, TOPK], global rows int64 [NQ, TOPK])
+
     def run(nsteps):
         if pool is None:
             for i in range(nsteps):
-                sharded.combine(local_search(i), TOPK)
+                last[0] = sharded.combine(local_search(i), TOPK)
             return
         futs = [pool.submit(local_search, i) for i in range(nsteps)]
         for f in futs:
-            sharded.combine(f.result(), TOPK)
+            last[0] = sharded.combine(f.result(), TOPK)
 
     def timed(nsteps):
         torch.cuda.synchronize()
@@ -1115,23 +1131,35 @@ def main():
         _barrier(world)
         return time.perf_counter() - t0
 
+    # the headline: warm up, then --steps timed steps with the searches in flight
     run(args.warmup)
-    # K7's launch time (roofline) from HIP events around the scan, taken while ONE search is in
-    # flight, so that a launch's span holds no other search's kernels; that run's rate is
-    # reported beside value as "one_search_in_flight"
-    nstreams_saved, pool_saved = nstreams, pool
-    nstreams, pool = 1, None
-    index.profile(1)
-    serial_dt = _max_over_ranks(timed(args.steps), world)
-    scan_ms, scan_n = index.profile(0)
+    dt = _max_over_ranks(timed(args.steps), world)
     unc, _ = index.last_stats()
-    nstreams, pool = nstreams_saved, pool_saved
-    dt = _max_over_ranks(timed(args.steps), world) if nstreams > 1 else serial_dt
+    if args.dump_outputs and rank == 0 and last[0] is not None:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        scores, rows = last[0][0], last[0][1]
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), scores.detach().cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "rows.npy"), rows.detach().cpu().numpy().astype(np.float64))
+    last[0] = None
+
+    # --full: K7's launch time (roofline) from HIP events around the scan, taken while ONE search is
+    # in flight, so that a launch's span holds no other search's kernels; that run's rate is
+    # reported beside value as "one_search_in_flight"
+    serial_dt = scan_ms = scan_n = None
+    if full:
+        nstreams_saved, pool_saved = nstreams, pool
+        nstreams, pool = 1, None
+        index.profile(1)
+        serial_dt = _max_over_ranks(timed(args.steps), world)
+        scan_ms, scan_n = index.profile(0)
+        nstreams, pool = nstreams_saved, pool_saved
     if pool is not None:
         pool.shutdown()
 
     # N > 1: what the communicator is, which devices the ranks drove, and the collective part of a
-    # step (all-gather of the per-shard (f64 score, row) lists + the K11 merge) timed alone
+    # step (all-gather of the per-shard (f64 score, row) lists + the K11 merge) timed alone (--full)
     comm = None
     if world > 1:
         backend = dist.get_backend()
@@ -1140,33 +1168,34 @@ def main():
         dist.all_gather_object(ranks, {"rank": rank, "local_device": local, "name": props.name,
                                        "pci_bus": getattr(props, "pci_bus_id", None),
                                        "host": os.uname().nodename})
-        loc = sharded.search_local(q, TOPK)
-        for _ in range(3):
-            sharded.combine(loc, TOPK)
-        reps = max(10, args.steps)
-        torch.cuda.synchronize()
-        _barrier(world)
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            sharded.combine(loc, TOPK)
-        torch.cuda.synchronize()
-        comm_dt = _max_over_ranks(time.perf_counter() - t0, world)
         comm = {"backend": backend, "collective": "RCCL" if backend == "nccl" else backend,
                 "world": dist.get_world_size(), "devices": ranks,
                 "distinct_devices": len({(r["host"], r["pci_bus"], r["local_device"]) for r in ranks}),
-                "allgather_merge_ms_per_step": round(comm_dt / reps * 1e3, 4),
                 "allgather_bytes_per_rank": NQ * TOPK * 16}
+        if full:
+            loc = sharded.search_local(q, TOPK)
+            for _ in range(3):
+                sharded.combine(loc, TOPK)
+            reps = max(10, args.steps)
+            torch.cuda.synchronize()
+            _barrier(world)
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                sharded.combine(loc, TOPK)
+            torch.cuda.synchronize()
+            comm_dt = _max_over_ranks(time.perf_counter() - t0, world)
+            comm["allgather_merge_ms_per_step"] = round(comm_dt / reps * 1e3, 4)
 
     ms_per_step = dt / args.steps * 1e3
     value = world * NQ * args.steps / dt
-    avg_scan_s = (scan_ms / max(scan_n, 1)) / 1e3
+    avg_scan_s = (scan_ms / max(scan_n, 1)) / 1e3 if full else 0.0
     flops_per_launch = 2.0 * NQ * ROWS_PER_GPU * DIM
     achieved_tflops = flops_per_launch / avg_scan_s / 1e12 if avg_scan_s > 0 else 0.0
 
     # the reference's call pattern hands host buffers over: same search with numpy queries in
     # and numpy results out (PCIe both ways + the final sync), reported beside value, never as it
     host_path = None
-    if world == 1:
+    if full and world == 1:
         qh = q.cpu().numpy()
         index.search(qh, TOPK)
         t0 = time.perf_counter()
@@ -1178,14 +1207,14 @@ def main():
                      "note": "numpy queries in / numpy results out (PCIe-inclusive, host buffers); not `value`"}
 
     call_pattern = None
-    if world == 1 and not args.no_call_pattern:
+    if full and world == 1 and not args.no_call_pattern:
         call_pattern = call_pattern_leg(index, q, reps=max(50, 10 * args.steps))
-    if world == 1 and not args.no_retrieve_pattern:
+    if full and world == 1 and not args.no_retrieve_pattern:
         call_pattern = call_pattern or {}
         call_pattern["retrieve"] = retrieve_pattern_leg(index, reps=max(50, 5 * args.steps))
 
     fusion = None
-    if not args.no_fusion:  # config 5 (all ranks take part: sharded corpora + all-gathers)
+    if full and not args.no_fusion:  # config 5 (all ranks take part: sharded corpora + all-gathers)
         del sharded
         index.close()
         torch.cuda.empty_cache()
@@ -1220,10 +1249,12 @@ def main():
                 "query_vector_pairs_per_s": round(value * ROWS_PER_GPU, 1),
                 "uncertified_queries_last_step": unc,
                 "searches_in_flight": nstreams,
-                "one_search_in_flight": {"queries_per_s": round(world * NQ * args.steps / serial_dt, 1),
-                                         "ms_per_step": round(serial_dt / args.steps * 1e3, 4)},
             },
-            "roofline": {
+        }
+        if full:
+            out["config"]["one_search_in_flight"] = {"queries_per_s": round(world * NQ * args.steps / serial_dt, 1),
+                                                     "ms_per_step": round(serial_dt / args.steps * 1e3, 4)}
+            out["roofline"] = {
                 "kernel": "knn_scan3_kernel<512, 0, 4> (K7 v3 main scan, MFMA 16x16x32; the 1/16 sample pre-pass is a separate launch, inside ms_per_step)",
                 "bound": "mfma",
                 "achieved": round(achieved_tflops, 2),
@@ -1237,14 +1268,13 @@ def main():
                 "avg_launch_ms": round(avg_scan_s * 1e3, 4),
                 "algorithmic_flops_per_launch": flops_per_launch,
                 "algorithmic_bytes_per_launch": ROWS_PER_GPU * DIM * 2 + NQ * DIM * 2,
-            },
-        }
-        if world == 1 and not args.no_ingest:
+            }
+        if full and world == 1 and not args.no_ingest:
             index_image, ingest = ingest_leg()
             out["call_pattern"] = dict(call_pattern or {}, ingest_embed_images_batch=ingest,
                                        index_image_nodes=index_image, index_text_nodes=index_text_leg())
             call_pattern = out["call_pattern"]
-        if not args.no_clip:
+        if full and not args.no_clip:
             clip = clip_leg(steps=max(30, args.steps), warmup=3, streams=clip_streams)  # single-GPU leg, rank 0; 30+ batches: three in flight reach steady state
             if clip is not None:
                 if not args.no_cpu_baseline:
@@ -1258,7 +1288,7 @@ def main():
             out["call_pattern"] = call_pattern
         if fusion is not None:
             out["fusion"] = fusion
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -7,7 +7,7 @@ import os
 import sys
 
 sys.path[:0] = [os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))]
-sys.argv = ["bench.py", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline"]
 import bench  # noqa: E402
 
 orig = bench.clip_leg
