@@ -300,6 +300,46 @@ int mrag_gemm_nt(const void* A, const void* W, const float* bias, void* C, int32
 int mrag_gemm_nt_kernel(const void* A, const void* W, const float* bias, void* C, int32_t M, int32_t N, int32_t K,
                         int32_t epilogue, int32_t kernel, void* stream);
 
+/* ---- building blocks: tests and timing -------------------------------------------------
+ * One launch of one encoder kernel each, on device pointers and a stream (NULL: the default
+ * stream); no allocation, no sync. Bad pointers / shapes return MRAG_ERR_ARG before any launch. */
+
+/* K2 LayerNorm: y[r] = (x[g(r)] - mean) * rsqrt(var + eps) * gamma + beta over rows of D <= 1024
+ * floats (x rows ldx floats apart, y rows dense); g(r) = gather[r] or r when gather is NULL;
+ * y32 (f32) and / or y16 (fp16) may be NULL, not both. In place (y32 == x) is allowed without a
+ * gather only: through a gather it is a race between rows and is rejected. D % 4 == 0 with
+ * ldx % 4 == 0 and 16-byte aligned pointers takes the vector kernel, anything else the scalar. */
+int mrag_layernorm(const float* x, const int32_t* gather, float* y32, void* y16, const float* gamma, const float* beta,
+                   int32_t rows, int32_t D, int32_t ldx, float eps, void* stream);
+/* K4 attention: out[B*L][H*head_dim] (fp16) = softmax(scale * q k^T) v per (sequence, head) from
+ * qkv[B*L][3*H*head_dim] (fp16, q | k | v); mask[B][L] (1 = keep the key) or NULL; causal != 0
+ * keeps key <= query. Query rows without a valid key give zeros. L in 1..512, head_dim 32 or 64.
+ * kernel: 0 the towers' rule (seq64 for 33 <= L <= 64, flash16 otherwise), 1 flash16, 2 seq64
+ * (rejected unless 33 <= L <= 64). Both kernels give the same bytes. */
+int mrag_attention(const void* qkv, void* out, const int32_t* mask, int32_t B, int32_t L, int32_t H, int32_t head_dim,
+                   int32_t causal, float scale, int32_t kernel, void* stream);
+/* K1 prologue: CLIP pixel normalisation + patch im2col. img[B][S][S][3] u8 -> out[B*(S/P)^2][3*P*P]
+ * fp16, K ordered (c, kh, kw). P % 8 == 0, S % P == 0; P = 32 with S % 16 == 0 and a 16-byte
+ * aligned img takes the vectorised kernel (the same bytes). */
+int mrag_vit_im2col(const uint8_t* img, void* out, int32_t B, int32_t S, int32_t P, void* stream);
+/* ViT token assembly + pre-LN: X[b*T + t] = LN((t == 0 ? cls : patch[b*(T-1) + t-1]) + pos[t]), f32,
+ * D % 4 == 0, D <= 1024. */
+int mrag_vit_embed_ln(const float* patch, const float* cls, const float* pos, const float* gamma, const float* beta,
+                      float* X, int32_t B, int32_t T, int32_t D, float eps, void* stream);
+/* X[b*T + t] = tok[clamp(ids, 0, vocab-1)] + pos[t] (+ type_tab[types != 0], row 0 when types is
+ * NULL; nothing when type_tab is NULL), f32, D % 4 == 0. */
+int mrag_token_embed(const int32_t* ids, const float* tok, const float* pos, const float* type_tab, const int32_t* types,
+                     float* X, int32_t B, int32_t T, int32_t D, int32_t vocab, void* stream);
+/* rows[b] = b*T + (first t with ids[b][t] == eos_id, 0 when absent; eos_id < 0: the first argmax). */
+int mrag_eos_rows(const int32_t* ids, int32_t B, int32_t T, int32_t eos_id, int32_t* rows, void* stream);
+/* out[b][d] = sum_t X[b][t][d] * m / max(sum_t m, 1e-9), m = (mask[b][t] != 0) or 1 when mask is NULL. */
+int mrag_mean_pool(const float* X, const int32_t* mask, float* out, int32_t B, int32_t T, int32_t D, void* stream);
+/* out[b][j] = sum_d tanh(pooled[b][d]) * Wc[j][d] + bc[j] (f32). */
+int mrag_cls_head(const float* pooled, const float* Wc, const float* bc, float* out, int32_t B, int32_t D, int32_t NL,
+                  void* stream);
+/* dst[b] = src[rows[b]] for rows of row_bytes bytes (row_bytes % 16 == 0, 16-byte aligned bases). */
+int mrag_gather_rows(const void* src, void* dst, const int32_t* rows, int32_t B, int32_t row_bytes, void* stream);
+
 
 #ifdef __cplusplus
 }

@@ -37,7 +37,7 @@ class _CConfig(ctypes.Structure):
 
 def _register_signatures():
     lib = _native.load()
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
     sigs = {
         "mrag_encoder_create": [ctypes.POINTER(_CConfig), i32, ctypes.POINTER(vp)],
         "mrag_encoder_destroy": [vp],
@@ -48,6 +48,16 @@ def _register_signatures():
         "mrag_gemm_nt": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
         "mrag_gemm_nt_kernel": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
         "mrag_encoder_score_pairs": [vp, vp, vp, vp, i32, i32, vp, i32, vp],
+        # building blocks (tests and timing)
+        "mrag_layernorm": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
+        "mrag_attention": [vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp],
+        "mrag_vit_im2col": [vp, vp, i32, i32, i32, vp],
+        "mrag_vit_embed_ln": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
+        "mrag_token_embed": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+        "mrag_eos_rows": [vp, i32, i32, i32, vp, vp],
+        "mrag_mean_pool": [vp, vp, vp, i32, i32, i32, vp],
+        "mrag_cls_head": [vp, vp, vp, vp, i32, i32, i32, vp],
+        "mrag_gather_rows": [vp, vp, vp, i32, i32, vp],
     }
     for name, args in sigs.items():
         try:
@@ -199,6 +209,96 @@ def gemm_nt(A, W, bias, C, epilogue: int, kernel: str = "auto"):
     return C
 
 
+# ---- building blocks: one kernel launch each on torch CUDA tensors (tests and timing) --------
+# Tensors are passed by their data_ptr (a view's offset base included) and the shape arguments
+# are explicit, so a test can hand over strided, offset or aliased buffers. Launches go to the
+# current torch stream; nothing is allocated or synchronised here.
+ATTENTION_KERNELS = {"auto": 0, "flash16": 1, "seq64": 2}
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _stream(t):
+    import torch
+
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def layernorm(x, gamma, beta, rows: int, D: int, ldx: Optional[int] = None, gather=None, y32=None, y16=None,
+              eps: float = 1e-5):
+    """K2: LayerNorm of ``rows`` rows of ``D`` floats (``ldx`` apart, default D) read from
+    ``x.data_ptr()``, through the optional int32 ``gather``, into ``y32`` (f32) and / or ``y16``."""
+    lib = _register_signatures()
+    _native.check(lib.mrag_layernorm(_ptr(x), _ptr(gather), _ptr(y32), _ptr(y16), _ptr(gamma), _ptr(beta), rows, D,
+                                     D if ldx is None else ldx, eps, _stream(x)), "mrag_layernorm")
+
+
+def attention(qkv, out, B: int, L: int, H: int, head_dim: int, mask=None, causal: bool = False,
+              scale: Optional[float] = None, kernel: str = "auto"):
+    """K4: ``out[B*L][H*head_dim]`` from fp16 ``qkv[B*L][3*H*head_dim]``; int32 ``mask[B][L]``
+    (1 = keep the key) or None; ``kernel`` one of ``ATTENTION_KERNELS``."""
+    lib = _register_signatures()
+    sc = head_dim ** -0.5 if scale is None else scale
+    _native.check(lib.mrag_attention(_ptr(qkv), _ptr(out), _ptr(mask), B, L, H, head_dim, int(causal), sc,
+                                     ATTENTION_KERNELS[kernel], _stream(qkv)), "mrag_attention")
+    return out
+
+
+def vit_im2col(img, out, B: int, S: int, P: int):
+    """K1 prologue: u8 ``img[B][S][S][3]`` -> fp16 ``out[B*(S/P)^2][3*P*P]`` (CLIP normalisation)."""
+    lib = _register_signatures()
+    _native.check(lib.mrag_vit_im2col(_ptr(img), _ptr(out), B, S, P, _stream(img)), "mrag_vit_im2col")
+    return out
+
+
+def vit_embed_ln(patch, cls, pos, gamma, beta, X, B: int, T: int, D: int, eps: float = 1e-5):
+    """``X[b*T + t] = LN((t == 0 ? cls : patch[b*(T-1) + t-1]) + pos[t])`` (f32)."""
+    lib = _register_signatures()
+    _native.check(lib.mrag_vit_embed_ln(_ptr(patch), _ptr(cls), _ptr(pos), _ptr(gamma), _ptr(beta), _ptr(X), B, T, D,
+                                        eps, _stream(X)), "mrag_vit_embed_ln")
+    return X
+
+
+def token_embed(ids, tok, pos, X, B: int, T: int, D: int, vocab: int, type_tab=None, types=None):
+    """``X[b*T + t] = tok[clamp(ids)] + pos[t] (+ type_tab[types != 0])`` (f32)."""
+    lib = _register_signatures()
+    _native.check(lib.mrag_token_embed(_ptr(ids), _ptr(tok), _ptr(pos), _ptr(type_tab), _ptr(types), _ptr(X), B, T, D,
+                                       vocab, _stream(X)), "mrag_token_embed")
+    return X
+
+
+def eos_rows(ids, rows, B: int, T: int, eos_id: int):
+    """``rows[b] = b*T +`` the first ``eos_id`` of int32 ``ids[b]`` (0 when absent; ``eos_id < 0``: the first argmax)."""
+    lib = _register_signatures()
+    _native.check(lib.mrag_eos_rows(_ptr(ids), B, T, eos_id, _ptr(rows), _stream(ids)), "mrag_eos_rows")
+    return rows
+
+
+def mean_pool(X, out, B: int, T: int, D: int, mask=None):
+    """Masked mean over T of f32 ``X[B][T][D]`` (sentence-transformers pooling)."""
+    lib = _register_signatures()
+    _native.check(lib.mrag_mean_pool(_ptr(X), _ptr(mask), _ptr(out), B, T, D, _stream(X)), "mrag_mean_pool")
+    return out
+
+
+def cls_head(pooled, Wc, bc, out, B: int, D: int, NL: int):
+    """``out[b][j] = sum_d tanh(pooled[b][d]) * Wc[j][d] + bc[j]`` (f32)."""
+    lib = _register_signatures()
+    _native.check(lib.mrag_cls_head(_ptr(pooled), _ptr(Wc), _ptr(bc), _ptr(out), B, D, NL, _stream(out)),
+                  "mrag_cls_head")
+    return out
+
+
+def gather_rows(src, dst, rows, B: int, row_bytes: int):
+    """``dst[b] = src[rows[b]]`` for rows of ``row_bytes`` bytes (a multiple of 16)."""
+    lib = _register_signatures()
+    _native.check(lib.mrag_gather_rows(_ptr(src), _ptr(dst), _ptr(rows), B, row_bytes, _stream(src)),
+                  "mrag_gather_rows")
+    return dst
+
+
 def load_encoder(cfg: EncoderConfig, model_name: Optional[str] = None, device: int = 0, seed: int = 0,
                  synthetic: Optional[bool] = None) -> GpuEncoder:
     """Encoder for a model name (local directory or cached hub snapshot). Synthetic weights
@@ -301,6 +401,7 @@ def smoke_encoders() -> None:
     assert e.shape == (3, 384) and np.all(np.isfinite(e))
 
 
-__all__ = ["GpuEncoder", "load_encoder", "gemm_nt", "bench_clip_images", "smoke_encoders", "CLIP_VISION_B32",
+__all__ = ["GpuEncoder", "load_encoder", "gemm_nt", "layernorm", "attention", "vit_im2col", "vit_embed_ln",
+           "token_embed", "eos_rows", "mean_pool", "cls_head", "gather_rows", "bench_clip_images", "smoke_encoders", "CLIP_VISION_B32",
            "CLIP_TEXT_B32", "MINILM_L6", "EncoderConfig", "param_specs", "vit_flops_per_image",
            "text_flops_per_sequence"]

@@ -962,4 +962,94 @@ int mrag_gemm_nt_kernel(const void* A, const void* W, const float* bias, void* C
   return launch_gemm(g, epilogue, (hipStream_t)stream, kernel);
 }
 
+// ---- building blocks: the other encoder kernels, one launch each (tests and timing) ----------
+// device pointers and a stream; no allocation, no sync
+
+int mrag_layernorm(const float* x, const int32_t* gather, float* y32, void* y16, const float* gamma, const float* beta,
+                   int32_t rows, int32_t D, int32_t ldx, float eps, void* stream) {
+  MRAG_REQUIRE(x && gamma && beta && (y32 || y16), "NULL pointer");
+  MRAG_REQUIRE(rows >= 0 && D > 0 && ldx >= D, "bad shape");
+  LayerNormArgs a{};
+  a.x = x;
+  a.gather = gather;
+  a.y32 = y32;
+  a.y16 = (_Float16*)y16;
+  a.gamma = gamma;
+  a.beta = beta;
+  a.rows = rows;
+  a.D = D;
+  a.ldx = ldx;
+  a.eps = eps;
+  return launch_layernorm(a, (hipStream_t)stream);
+}
+
+int mrag_attention(const void* qkv, void* out, const int32_t* mask, int32_t B, int32_t L, int32_t H, int32_t head_dim,
+                   int32_t causal, float scale, int32_t kernel, void* stream) {
+  MRAG_REQUIRE(qkv && out, "NULL pointer");
+  MRAG_REQUIRE(B >= 0 && L >= 1 && H >= 1, "bad shape");
+  MRAG_REQUIRE((((uintptr_t)qkv | (uintptr_t)out) & 15) == 0, "attention: qkv and out must be 16-byte aligned");
+  AttentionArgs a{};
+  a.qkv = (const _Float16*)qkv;
+  a.out = (_Float16*)out;
+  a.mask = mask;
+  a.B = B;
+  a.L = L;
+  a.H = H;
+  a.causal = causal != 0;
+  a.scale = scale;
+  return launch_attention(a, head_dim, (hipStream_t)stream, kernel);
+}
+
+int mrag_vit_im2col(const uint8_t* img, void* out, int32_t B, int32_t S, int32_t P, void* stream) {
+  MRAG_REQUIRE(img && out, "NULL pointer");
+  MRAG_REQUIRE(B >= 0 && P > 0 && P % 8 == 0 && S >= P && S % P == 0, "vit_im2col: B=%d S=%d P=%d unsupported", B, S, P);
+  MRAG_REQUIRE(((uintptr_t)out & 15) == 0, "vit_im2col: out must be 16-byte aligned");
+  return launch_vit_im2col(img, (_Float16*)out, B, S, P, (hipStream_t)stream);
+}
+
+int mrag_vit_embed_ln(const float* patch, const float* cls, const float* pos, const float* gamma, const float* beta,
+                      float* X, int32_t B, int32_t T, int32_t D, float eps, void* stream) {
+  MRAG_REQUIRE(patch && cls && pos && gamma && beta && X, "NULL pointer");
+  MRAG_REQUIRE(B >= 0 && T >= 1 && D > 0, "bad shape");
+  MRAG_REQUIRE((((uintptr_t)patch | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)X) &
+                15) == 0,
+               "vit_embed_ln: pointers must be 16-byte aligned");
+  return launch_vit_embed_ln(patch, cls, pos, gamma, beta, X, B, T, D, eps, (hipStream_t)stream);
+}
+
+int mrag_token_embed(const int32_t* ids, const float* tok, const float* pos, const float* type_tab, const int32_t* types,
+                     float* X, int32_t B, int32_t T, int32_t D, int32_t vocab, void* stream) {
+  MRAG_REQUIRE(ids && tok && pos && X, "NULL pointer");
+  MRAG_REQUIRE(B >= 0 && T >= 0 && D >= 0 && vocab >= 1, "bad shape");
+  MRAG_REQUIRE((((uintptr_t)tok | (uintptr_t)pos | (uintptr_t)type_tab | (uintptr_t)X) & 15) == 0,
+               "token_embed: tables and X must be 16-byte aligned");
+  return launch_token_embed(ids, tok, pos, type_tab, types, X, B, T, D, vocab, (hipStream_t)stream);
+}
+
+int mrag_eos_rows(const int32_t* ids, int32_t B, int32_t T, int32_t eos_id, int32_t* rows, void* stream) {
+  MRAG_REQUIRE(ids && rows, "NULL pointer");
+  MRAG_REQUIRE(B >= 0 && T >= 1, "bad shape");
+  return launch_eos_rows(ids, B, T, eos_id, rows, (hipStream_t)stream);
+}
+
+int mrag_mean_pool(const float* X, const int32_t* mask, float* out, int32_t B, int32_t T, int32_t D, void* stream) {
+  MRAG_REQUIRE(X && out, "NULL pointer");
+  MRAG_REQUIRE(B >= 0 && T >= 0 && D >= 0, "bad shape");
+  return launch_mean_pool(X, mask, out, B, T, D, (hipStream_t)stream);
+}
+
+int mrag_cls_head(const float* pooled, const float* Wc, const float* bc, float* out, int32_t B, int32_t D, int32_t NL,
+                  void* stream) {
+  MRAG_REQUIRE(pooled && Wc && bc && out, "NULL pointer");
+  MRAG_REQUIRE(B >= 0 && D >= 0 && NL >= 0, "bad shape");
+  return launch_cls_head(pooled, Wc, bc, out, B, D, NL, (hipStream_t)stream);
+}
+
+int mrag_gather_rows(const void* src, void* dst, const int32_t* rows, int32_t B, int32_t row_bytes, void* stream) {
+  MRAG_REQUIRE(src && dst && rows, "NULL pointer");
+  MRAG_REQUIRE(B >= 0 && row_bytes > 0, "bad shape");
+  MRAG_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "gather_rows: src and dst must be 16-byte aligned");
+  return launch_gather_rows(src, dst, rows, B, row_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

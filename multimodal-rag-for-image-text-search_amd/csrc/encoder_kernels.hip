@@ -1090,24 +1090,7 @@ __device__ __forceinline__ void ln_row4(f32x4 (&v)[4], int lane, int D, float ep
   ln_row4p(v, lane, D, eps, g4, b4, y32, y16);
 }
 
-// One wave per row: the row's loads and the gamma / beta chunks are issued before the first
-// reduction (two rows per wave measured slower: 14.3 vs 12.3 us per ViT LayerNorm).
-__global__ __launch_bounds__(256) void layernorm4_kernel(LayerNormArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= a.rows) return;
-  const int src = a.gather ? a.gather[r] : r;
-  const f32x4* x = (const f32x4*)(a.x + (size_t)src * a.ldx);
-  f32x4 v[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = lane + 64 * j < (a.D >> 2) ? x[lane + 64 * j] : f32x4{};
-  f32x4 g4[4], b4[4];
-  ln_params4(lane, a.D, a.gamma, a.beta, g4, b4);
-  ln_row4p(v, lane, a.D, a.eps, g4, b4, a.y32 ? a.y32 + (size_t)r * a.D : nullptr,
-           a.y16 ? a.y16 + (size_t)r * a.D : nullptr);
-}
-
-// K2 streaming form (the same arithmetic, bit-identical to layernorm4_kernel): a persistent grid
+// K2 streaming form of the vectorised rows: a persistent grid
 // of LN_WG_PER_CU workgroups per CU; a wave walks rows w, w + W, ... (W = the grid's waves),
 // loads its gamma / beta chunks once and issues the next row's loads before this row's
 // reductions, so each wave keeps a row in flight while it reduces the previous one (one row per
@@ -1735,17 +1718,19 @@ int launch_layernorm(const LayerNormArgs& a, hipStream_t s) {
   MRAG_REQUIRE(a.D > 0 && a.D <= 1024, "layernorm: D=%d unsupported", a.D);
   const bool vec4 = a.D % 4 == 0 && a.ldx % 4 == 0 && ((uintptr_t)a.x & 15) == 0 && ((uintptr_t)a.gamma & 15) == 0 &&
                     ((uintptr_t)a.beta & 15) == 0 && ((uintptr_t)a.y32 & 15) == 0 && ((uintptr_t)a.y16 & 7) == 0;
-  // in place through a gather, two output rows could read one input row another wave overwrites
-  const bool alias = a.gather && a.y32 == a.x;
-  if (vec4 && !alias) {
+  // in place through a gather, the wave writing row r can overwrite a row another wave has yet to
+  // read (whatever the kernel: rows are written by different waves in no order)
+  MRAG_REQUIRE(!(a.gather && a.y32 == a.x), "layernorm: in place (y32 == x) through a gather is a race");
+  // output rows are dense: in place over padded input rows, row r would land inside input row r - 1
+  MRAG_REQUIRE(!(a.y32 == a.x && a.ldx != a.D), "layernorm: in place (y32 == x) needs ldx == D (ldx=%d, D=%d)", a.ldx,
+               a.D);
+  if (vec4) {
     const int nb = std::min((a.rows + 3) / 4, num_cus() * LN_WG_PER_CU);
     if (a.gather)
       hipLaunchKernelGGL(layernorm_stream_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, a);
     else
       hipLaunchKernelGGL(layernorm_stream_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, a);
-  } else if (vec4)
-    hipLaunchKernelGGL(layernorm4_kernel, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, s, a);
-  else
+  } else
     hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, s, a);
   MRAG_CHECK_LAUNCH();
   return MRAG_OK;
@@ -1761,13 +1746,17 @@ int launch_vit_embed_ln(const float* patch, const float* cls, const float* pos, 
   return MRAG_OK;
 }
 
-int launch_attention(const AttentionArgs& a, int dh, hipStream_t s) {
+int launch_attention(const AttentionArgs& a, int dh, hipStream_t s, int kernel) {
   if (a.B <= 0) return MRAG_OK;
   MRAG_REQUIRE(a.L >= 1 && a.L <= 512, "attention: L=%d unsupported (1..512)", a.L);
   MRAG_REQUIRE(dh == 64 || dh == 32, "attention: head_dim %d unsupported (32, 64)", dh);
   const int64_t items = (int64_t)a.B * a.H * ((a.L + 15) / 16);
   MRAG_REQUIRE(items < (1ll << 33), "attention: batch too large");
-  if (a.L > 32 && a.L <= 64) {  // one workgroup per (sequence, head): the ViT's 50 tokens
+  MRAG_REQUIRE(kernel >= ATTN_AUTO && kernel <= ATTN_SEQ64, "attention: bad kernel %d", kernel);
+  MRAG_REQUIRE(kernel != ATTN_SEQ64 || (a.L > 32 && a.L <= 64), "attention: the seq64 kernel needs 33 <= L <= 64 (L=%d)",
+               a.L);
+  // one workgroup per (sequence, head): the ViT's 50 tokens
+  if (kernel == ATTN_SEQ64 || (kernel == ATTN_AUTO && a.L > 32 && a.L <= 64)) {
     hipLaunchKernelGGL(dh == 64 ? attention_seq64_kernel<64> : attention_seq64_kernel<32>,
                        dim3((unsigned)((int64_t)a.B * a.H)), dim3(256), 0, s, a);
   } else {

@@ -228,6 +228,19 @@ def test_gemm_shapes_every_epilogue(cuda):
             assert torch.equal(outs[0], outs[1]), ("nondeterministic", M, N, K, epi)
             err = (C.float() - r).abs().max().item() / r.abs().max().item()
             assert err < (2e-3 if epi <= 2 else 2e-5), (M, N, K, epi, err)
+    # bias == NULL (no tower passes it): K3 and K3d forced, an f16 and an f32 epilogue, against A W^T
+    for kern, (M, N, K) in (("k3", (300, 256, 64)), ("k3d", (1100, 768, 768))):
+        g = torch.Generator(device="cuda").manual_seed(K)
+        A = (torch.randn(M, K, generator=g, device="cuda") * 0.5).half()
+        W = (torch.randn(N, K, generator=g, device="cuda") * 0.05).half()
+        ref = A.float() @ W.float().t()
+        for epi in (0, 4):
+            C = torch.full((M, N), float("nan"), dtype=torch.float16 if epi == 0 else torch.float32, device="cuda")
+            gemm_nt(A, W, None, C, epi, kernel=kern)
+            torch.cuda.synchronize()
+            assert not torch.isnan(C.float()).any(), (kern, epi)
+            err = (C.float() - ref).abs().max().item() / ref.abs().max().item()
+            assert err < (2e-3 if epi == 0 else 2e-5), (kern, "bias=None", epi, err)
 
 
 @pytest.mark.parametrize("N,K", [(384, 384), (384, 1536), (1152, 384), (1536, 384), (512, 2048), (2048, 512),
@@ -274,16 +287,31 @@ def test_gemm_skinny_rows_equal_k3(cuda, N, K):
             assert torch.equal(C, big[:M]), ("skinny != K3 rows", M, N, K, epi)
             err = (C.float() - ref[:M]).abs().max().item() / ref[:M].abs().max().item()
             assert err < (2e-3 if epi <= 2 else 2e-5), (M, N, K, epi, err)
+    if (N, K) == (384, 384):  # bias == NULL on K3s: the same bytes as K3's rows, and A W^T
+        ref = A.float() @ W.float().t()
+        outs = {}
+        for kern, M in (("k3", Mb), ("k3s", 17)):
+            C = torch.full((M, N), float("nan"), dtype=torch.float16, device=cuda)
+            gemm_nt(A[:M].contiguous(), W, None, C, 0, kernel=kern)
+            outs[kern] = C
+        torch.cuda.synchronize()
+        assert not torch.isnan(outs["k3s"].float()).any()
+        assert torch.equal(outs["k3s"], outs["k3"][:17]), "skinny != K3 rows, bias=None"
+        err = (outs["k3s"].float() - ref[:17]).abs().max().item() / ref[:17].abs().max().item()
+        assert err < 2e-3, ("bias=None", err)
 
 
-@pytest.mark.parametrize("N,K", [(1536, 512), (2048, 512), (1152, 384), (1536, 384), (768, 512), (384, 384)])
+@pytest.mark.parametrize("N,K", [(1536, 512), (2048, 512), (1152, 384), (1536, 384), (768, 512), (384, 384),
+                                 (1152, 512), (384, 512)])
 def test_gemm_weight_stationary_equals_k3(cuda, N, K):
     """K3w (the weight-stationary kernel the text towers' q|k|v and fc1 take at K 384 / 512) against
     K3 forced on the same operands: bit-identical for the three f16 epilogues (one accumulation
     order, K3's epilogue), with M a multiple of the 64-row tile, ragged (the last tile partly past
     M: clamped loads, no stores), and small enough that some row ranges own no tile or one tile;
     and within K3's tolerance of a torch fp32 product. The automatic rule takes K3w for these
-    shapes at M >= 4096."""
+    shapes at M >= 4096. (1152, 512) and (384, 512) are K = 512 with N % 192 == 0 only: three
+    64-column blocks per wave at the 16-step K. Without a bias (no tower passes NULL): the same
+    checks at one K = 384 and one K = 512 shape."""
     import torch
 
     from app.encoders import gemm_nt
@@ -307,6 +335,20 @@ def test_gemm_weight_stationary_equals_k3(cuda, N, K):
             if epi == 0:
                 err = (outs["k3w"].float() - ref).abs().max().item() / ref.abs().max().item()
                 assert err < 2e-3, (M, N, K, err)
+        if M == 4100 and (N, K) in ((1152, 384), (384, 512)):
+            ref0 = A.float() @ W.float().t()
+            for epi in range(3):
+                outs = {}
+                for kern in ("k3", "k3w"):
+                    C = torch.full((M, N), float("nan"), dtype=torch.float16, device=cuda)
+                    gemm_nt(A, W, None, C, epi, kernel=kern)
+                    outs[kern] = C
+                torch.cuda.synchronize()
+                assert not torch.isnan(outs["k3w"].float()).any(), ("bias=None", N, K, epi)
+                assert torch.equal(outs["k3w"], outs["k3"]), ("K3w != K3, bias=None", N, K, epi)
+                if epi == 0:
+                    err = (outs["k3w"].float() - ref0).abs().max().item() / ref0.abs().max().item()
+                    assert err < 2e-3, ("bias=None", N, K, err)
 
 
 def test_gelu_erf_epilogue_sweep(cuda):
