@@ -82,6 +82,14 @@ struct ScanParams {
   // v3: requested k (publishing rule) and per-(split, query) bound on every dropped row
   int k;
   float* part_tau;
+  // counting sample pass (v3 MODE 2): every sample_stride-th tile of a split, all of them; each
+  // lane's record per query, [split][Qp][4 lane groups] x {m1, m2, m3, 0} (packed group maxima,
+  // see MODE 2), with the group id in the low bits that rec_keep clears. skip_magic != 0: the
+  // main scan (MODE 0) walks only the other tiles; the value is 2^32 / (sample_stride - 1)
+  // rounded up (exact quotients for tile counts below 2^32 / sample_stride).
+  uint32_t* rec;
+  uint32_t rec_keep;
+  uint32_t skip_magic;
 };
 
 template <int KL>
@@ -453,6 +461,11 @@ __device__ __forceinline__ void mfma16_guard(f32x4 (&acc)[4][1]) {
 // per-(split, query, lane group) maxima go to part_s for theta_init_kernel, which seeds the
 // shared threshold with the k-th largest of them.
 //
+// MODE 2 = the counting sample pass (k <= 16): every sample_stride-th tile of the split, all of
+// them, keeping per lane and query block the three largest group maxima with their group ids
+// (rm1..rm3 below); sample_resolve_kernel seeds the threshold from them and lists the sampled
+// rows above it, and MODE 0 then skips those tiles.
+//
 // QB = query blocks of 16 per wave: 4 (a workgroup holds 256 queries; the MFMA-bound batches)
 // or 1 (64 queries: the small batches of the reference's own call pattern, one query per
 // retrieve_text / retrieve_images, app/ml/retrieve.py:53,84). With one block a tile costs a
@@ -557,13 +570,37 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
 
   int my_tiles = (split < p.ntiles) ? (p.ntiles - 1 - split) / p.splits + 1 : 0;
   int tstep = p.splits;
+  // After a counting sample pass (MODE 2 took every sample_stride-th tile of the split, the
+  // first one included) MODE 0 walks the others: the n-th of them is the split's tile
+  // n + n / (stride - 1) + 1, the division as a multiply-high by skip_magic (0: walk every tile).
+  uint32_t skip_magic = 0u;
+  int skip_off = 0;
   if constexpr (MODE == 1) {
     my_tiles = min(my_tiles, p.sample_tiles);
     tstep = p.splits * p.sample_stride;
+  } else if constexpr (MODE == 2) {
+    my_tiles = (my_tiles + p.sample_stride - 1) / p.sample_stride;
+    tstep = p.splits * p.sample_stride;
+  } else if constexpr (QB == 4) {
+    if (p.skip_magic != 0u) {
+      my_tiles -= (my_tiles + p.sample_stride - 1) / p.sample_stride;
+      skip_magic = p.skip_magic;
+      skip_off = 1;
+    }
   }
+  auto tile_of = [&](int it) { return split + (it + (int)__umulhi((uint32_t)it, skip_magic) + skip_off) * tstep; };
   float smax[QB];
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) smax[qb] = -INFINITY;
+  // MODE 2: per query block the lane's three largest group maxima m1 >= m2 >= m3 over its sampled
+  // 4-row groups, as unsigned bit patterns: max(score, 0) with the low bits replaced by the group
+  // id (4 x sample-tile ordinal + row block). Non-negative floats order like their bits, so three
+  // integer min / max / med3 carry value and id together. m1 and m2 name two groups; m3 bounds
+  // every other group of the lane (with the id bits set: an upper bound).
+  uint32_t rm1[QB], rm2[QB], rm3[QB];
+#pragma unroll
+  for (int qb = 0; qb < QB; ++qb) rm1[qb] = rm2[qb] = rm3[qb] = 0u;
+  int pid = 0;  // 4 x ordinal of the tile whose scores epi_group reads
 
   auto stage_piece = [&](int buf, int tile, int i, int lane_t) {
     const char* gt = (const char*)p.x16 + (size_t)tile * TILE_BYTES;
@@ -589,6 +626,19 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
     constexpr int Y = decltype(y_c)::value;
     constexpr int qb = G >> 2, rb = G & 3;
     f32x4& av = acc[Y][rb][qb];
+    if constexpr (MODE == 2) {
+      // 7 VALU ops: as signed integers every negative float (and the -inf of a masked row) lies
+      // below 0 and the non-negative ones keep their order, so max3_i32 twice is max(scores, 0)
+      // (bit casts of the accumulators: integer ops need no canonicalising of inline-asm outputs)
+      const int gmi = max(max(max(__float_as_int(av[0]), __float_as_int(av[1])), __float_as_int(av[2])),
+                          max(__float_as_int(av[3]), 0));
+      const uint32_t v = ((uint32_t)gmi & p.rec_keep) | (uint32_t)(pid + rb);
+      const uint32_t m1 = rm1[qb], m2 = rm2[qb];
+      rm3[qb] = max(rm3[qb], min(v, m2));
+      asm("v_med3_u32 %0, %1, %2, %3" : "=v"(rm2[qb]) : "v"(v), "v"(m1), "v"(m2));
+      rm1[qb] = max(m1, v);
+      return;
+    }
     // two VALU ops for the group maximum: the accumulators come out of inline asm, so fmaxf
     // would first canonicalise each operand (v_max x, x); scores are never NaN
     float gm;
@@ -679,9 +729,9 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
     constexpr int X = decltype(x_c)::value;
     constexpr int Y = 1 - X;
     K7_STAMP(st0);
-    const int tile = split + it * tstep;
+    const int tile = tile_of(it);
     const bool has_next = it + 1 < my_tiles;
-    const int ntile = has_next ? tile + tstep : tile;
+    const int ntile = has_next ? tile_of(it + 1) : tile;
     const char* gw = (const char*)p.x16 + (size_t)ntile * TILE_BYTES + (size_t)w * GLDS_PER_WAVE * ROW_BYTES;
     uint32_t ldsw = lds_base + Y * TILE_BYTES + w * GLDS_PER_WAVE * 1024;
     asm volatile("" : "+s"(gw), "+s"(ldsw));
@@ -793,6 +843,7 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
         }
     }
     prow = tile * TILE_ROWS + 4 * g4;
+    if constexpr (MODE == 2) pid = 4 * it;
     end_of_tile(true);
 #ifdef MRAG_K7_STAMPS
     if constexpr (QB == 4) {
@@ -819,8 +870,8 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
   }
   if (my_tiles > 0) {
 #pragma unroll
-    for (int i = 0; i < GLDS_PER_WAVE; ++i) stage_piece(0, split, i, lane);
-    stage_labels(0, split);
+    for (int i = 0; i < GLDS_PER_WAVE; ++i) stage_piece(0, tile_of(0), i, lane);
+    stage_labels(0, tile_of(0));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int it = 0; it < my_tiles; it += 2) {
@@ -847,6 +898,15 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
       // four maxima per (split, query) over disjoint rows: lane group g4 = 0..3 (theta_init
       // takes the k-th largest of all splits' values: a valid lower bound, tighter than two)
       p.part_s[((size_t)split * p.Qp + slot0 + 16 * qb) * 4 + g4] = smax[qb];
+    }
+    return;
+  }
+  if constexpr (MODE == 2) {
+#pragma unroll
+    for (int qb = 0; qb < QB; ++qb) {
+      using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
+      *(u32x4*)(p.rec + (((size_t)split * p.Qp + slot0 + 16 * qb) * 4 + g4) * 4) =
+          u32x4{rm1[qb], rm2[qb], rm3[qb], 0u};
     }
     return;
   }
@@ -940,6 +1000,153 @@ __global__ __launch_bounds__(64) void theta_init_kernel(const float* __restrict_
   if (lane == 0) theta[q] = (kth == -INFINITY) ? 0u : mrag_f2ord(kth - THETA_SEED_MARGIN);
 }
 
+// Seed and resolve after the counting sample pass (MODE 2), one wave per query.
+//  * Seed: the k-th largest of all recorded m1 and m2 of the query (id bits cleared: a lower
+//    bound on that group's maximum). They are maxima of disjoint 4-row groups, so k distinct rows
+//    score at least that; theta = that - THETA_SEED_MARGIN, as theta_init_kernel. Fewer than k
+//    positive maxima: no seed.
+//  * Resolve: every recorded group whose maximum (id bits set: an upper bound) can exceed theta
+//    is scored again, four groups = 16 rows per step, from the same fp16 rows and query the MFMA
+//    read, in f32; rows above theta that pass the label filter go to XLISTS extra 8-entry lists of
+//    the query, splits [splits, splits + XLISTS) of part_s / part_i. Beyond XCAP rows the best
+//    are kept and the best dropped score joins the bound below.
+//  * Bound: part_tau of the first extra list = max over the query's lanes of m3 (every sampled
+//    row in neither recorded group of its lane scores at most that) and of the dropped rows. A
+//    recorded group that was not scored, and a scored row not listed, lie at or below theta,
+//    which K8 has in T. A record whose value bits are all zero (maximum <= 0, or below the
+//    smallest kept value) is not scored: m3 with its id bits set bounds it too.
+struct ResolveParams {
+  const uint32_t* rec;
+  uint32_t idmask;
+  int splits, Qp, k, DP, tile_step, label_filter;  // tile_step = splits * sample stride
+  const _Float16* x16;
+  const _Float16* q16;
+  const int32_t* labels;
+  uint32_t* theta;
+  float* part_s;
+  int32_t* part_i;
+  float* part_tau;
+};
+constexpr int XLISTS = 4, XCAP = XLISTS * 8;
+constexpr int REC_ID_BITS_MAX = 10;  // id field of a packed record entry (qrec packs beside it)
+
+__global__ __launch_bounds__(64) void sample_resolve_kernel(ResolveParams p) {
+  using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
+  constexpr int PER_LANE = 32;  // splits <= 256: lane l holds splits l, l + 64, ...: 4 x 4 lane groups x {m1, m2}
+  __shared__ uint32_t qrec[64 * PER_LANE];  // groups to score: split << 12 | lane group << 10 | id
+  __shared__ float xs[XCAP + 16];
+  __shared__ int xr[XCAP + 16];
+  const int q = blockIdx.x, lane = threadIdx.x;
+  const uint64_t lt = (1ull << lane) - 1;
+  uint32_t u[PER_LANE], m3 = 0u;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int sp = lane + 64 * t;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const u32x4 r = sp < p.splits ? *(const u32x4*)(p.rec + (((size_t)sp * p.Qp + q) * 4 + g) * 4)
+                                    : u32x4{0u, 0u, 0u, 0u};
+      u[8 * t + 2 * g] = r[0];
+      u[8 * t + 2 * g + 1] = r[1];
+      m3 = max(m3, r[2]);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m3 = max(m3, (uint32_t)__shfl_xor((int)m3, off));
+
+  // k-th largest entry, duplicates counted: at most k rounds of "largest below the previous one"
+  uint32_t kth = 0u, prev = ~0u;
+  int above = 0;
+  for (int r = 0; r < p.k; ++r) {
+    uint32_t best = 0u;
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < PER_LANE; ++i) best = max(best, u[i] < prev ? u[i] : 0u);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, off));
+    if (best <= p.idmask) break;  // no positive maximum left
+#pragma unroll
+    for (int i = 0; i < PER_LANE; ++i) c += u[i] == best;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    above += c;
+    if (above >= p.k) {
+      kth = best;
+      break;
+    }
+    prev = best;
+  }
+  float theta_f = -INFINITY;
+  if (kth != 0u) theta_f = __uint_as_float(kth & ~p.idmask) - THETA_SEED_MARGIN;
+  if (lane == 0) p.theta[q] = kth != 0u ? mrag_f2ord(theta_f) : 0u;
+
+  int nrec = 0;
+#pragma unroll
+  for (int i = 0; i < PER_LANE; ++i) {
+    const bool qf = u[i] > p.idmask && __uint_as_float(u[i] | p.idmask) > theta_f;
+    const uint64_t b = __ballot(qf);
+    if (qf)
+      qrec[nrec + __popcll(b & lt)] =
+          ((uint32_t)(lane + 64 * (i >> 3)) << 12) | ((uint32_t)((i >> 1) & 3) << 10) | (u[i] & p.idmask);
+    nrec += __popcll(b);
+  }
+  __syncthreads();
+
+  const int lab_lo = p.label_filter == MRAG_LABEL_ANY ? 0 : p.label_filter;
+  const uint32_t lab_span = p.label_filter == MRAG_LABEL_ANY ? 0x7fffffffu : 0u;
+  const int gsel = lane >> 4, rr = (lane >> 2) & 3, sub = lane & 3;
+  const half8* qrow = (const half8*)(p.q16 + (size_t)q * p.DP);
+  int cnt = 0;
+  float tau_drop = -INFINITY;
+  for (int base = 0; base < nrec; base += 4) {
+    const bool have = base + gsel < nrec;
+    const uint32_t pk = qrec[have ? base + gsel : base];
+    const int sp = (int)(pk >> 12), g = (int)(pk >> 10) & 3, id = (int)(pk & p.idmask);
+    const int64_t row = (int64_t)(sp + (id >> 2) * p.tile_step) * TILE_ROWS + 16 * (id & 3) + 4 * g + rr;
+    const half8* xrow = (const half8*)(p.x16 + row * p.DP);
+    float acc = 0.f;
+    for (int c = sub; c < p.DP / 8; c += 4) {
+      const half8 a = xrow[c], b = qrow[c];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc += (float)a[e] * (float)b[e];
+    }
+    acc += __shfl_xor(acc, 1);
+    acc += __shfl_xor(acc, 2);
+    const int lab = p.labels[row];
+    const bool take = have && sub == 0 && (uint32_t)(lab - lab_lo) <= lab_span && acc > theta_f;
+    const uint64_t b = __ballot(take);
+    if (take) {
+      const int pos = cnt + __popcll(b & lt);
+      xs[pos] = acc;
+      xr[pos] = (int)row;
+    }
+    cnt += __popcll(b);
+    __syncthreads();
+    while (cnt > XCAP) {  // drop the lowest; its score bounds it
+      const float v = lane < cnt ? xs[lane] : INFINITY;
+      float wmin = v;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) wmin = fminf(wmin, __shfl_xor(wmin, off));
+      const int holder = (int)__builtin_ctzll(__ballot(v == wmin));
+      tau_drop = fmaxf(tau_drop, wmin);
+      if (lane == 0) {
+        xs[holder] = xs[cnt - 1];
+        xr[holder] = xr[cnt - 1];
+      }
+      --cnt;
+      __syncthreads();
+    }
+  }
+  if (lane < XCAP) {
+    const size_t o = ((size_t)(p.splits + lane / 8) * p.Qp + q) * 8 + (lane & 7);
+    p.part_s[o] = lane < cnt ? xs[lane] : -INFINITY;
+    p.part_i[o] = lane < cnt ? xr[lane] : -1;
+  }
+  if (lane < XLISTS)
+    p.part_tau[(size_t)(p.splits + lane) * p.Qp + q] =
+        lane == 0 ? fmaxf(__uint_as_float(m3 | p.idmask), tau_drop) : -INFINITY;
+}
+
 // ---------------------------------------------------------------------------
 // Exact rescoring: mrag_knn::exact_cosine16 (knn_generic.h), shared with K7g.
 using mrag_knn::exact_cosine16;
@@ -948,6 +1155,8 @@ struct MergeParams {
   const float* part_s;
   const int32_t* part_i;
   int splits, KL, Qp, nq, k, M, R, Mp;
+  int scan_splits;  // the first scan_splits lists are a scan's (a full one's last entry bounds what
+                    // it dropped); the others are the resolved sample rows, bounded by part_tau alone
   const float* q32;
   const double* qn;
   const float* x32;
@@ -1059,7 +1268,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void knn_merge_kernel(MergeParams p)
 
   float tau = -INFINITY;
   int valid = 0;
-  const int ntot = p.splits * p.KL;
+  const int ntot = p.splits * p.KL, nscan = p.scan_splits * p.KL;
   // candidate e of the union: the row and score are read together and unconditionally (a
   // clamped slot past the union), so a chunk costs one memory round trip and the next chunk's
   // reads can be in flight during this one's sort; invalid -> ~0 (sorts last)
@@ -1076,7 +1285,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void knn_merge_kernel(MergeParams p)
   auto make_key = [&](int e, Raw v) -> uint64_t {
     if (e >= ntot || v.r < 0) return ~0ull;
     ++valid;
-    if (e % p.KL == p.KL - 1) tau = fmaxf(tau, v.s);
+    if (e % p.KL == p.KL - 1 && e < nscan) tau = fmaxf(tau, v.s);
     return ((uint64_t)(~mrag_f2ord(v.s)) << 32) | (uint32_t)v.r;
   };
   auto load_key = [&](int e) -> uint64_t { return make_key(e, load_raw(e)); };
@@ -1586,10 +1795,11 @@ scan_fn get_scan3m(int DP) {
     default: return nullptr;
   }
 }
-// the sample pre-pass (MODE 1) exists for the 256-query groups only (K7s runs without it)
-scan_fn get_scan3(int DP, bool sample, int qb) {
-  if (qb == 1) return sample ? nullptr : get_scan3m<0, 1>(DP);
-  return sample ? get_scan3m<1, 4>(DP) : get_scan3m<0, 4>(DP);
+// the sample passes (MODE 1: seed only; MODE 2: counting) exist for the 256-query groups only (K7s
+// runs without them)
+scan_fn get_scan3(int DP, int mode, int qb) {
+  if (qb == 1) return mode ? nullptr : get_scan3m<0, 1>(DP);
+  return mode == 2 ? get_scan3m<2, 4>(DP) : mode == 1 ? get_scan3m<1, 4>(DP) : get_scan3m<0, 4>(DP);
 }
 
 // Query blocks per wave of the v3 scan for a batch: 1 (K7s, 64 queries per workgroup) while the
@@ -1600,6 +1810,10 @@ int scan3_qb(int64_t nq) { return nq <= 64 ? 1 : 4; }
 // k x stride, so k > 16 samples every 4th tile (512k x 512, k = 50: search 0.824 -> 0.736 ms,
 // scan 0.659 -> 0.501; stride 8: 0.748; notes/knn_scan_experiments.md).
 int sample_stride_for(int k) { return k > 16 ? 4 : SAMPLE_STRIDE; }
+// k <= 16: the counting sample pass (MODE 2 + sample_resolve_kernel) takes its tiles for good and
+// the main scan skips them; k > 16 keeps the seed-only pass over every 4th tile and a main scan
+// over all tiles (the rows above its seed, about k x stride, would not fit the extra lists).
+bool counting_sample_for(int k) { return k <= 16; }
 
 scan_fn get_scan(int DP, int KL, bool collect) {
   switch (DP) {
@@ -1626,7 +1840,7 @@ int64_t next_pow2(int64_t x) {
 // beside the other's scan (bench.py runs the kNN leg that way on one GPU).
 struct SearchCtx {
   DevBuf qin, q32, qn, q16, part_s, part_i, thresh, fail_list, counters, cand_cnt, cand, scratch;
-  DevBuf out_s, out_s64, out_r, theta, part_tau;
+  DevBuf out_s, out_s64, out_r, theta, part_tau, rec;
   int32_t* host_counters = nullptr;  // pinned [2]: fail_cnt, overflow
   int32_t* host_fail = nullptr;      // coherent pinned [4]: [0] = some query failed K8's certificate
   hipEvent_t done = nullptr;         // end of the search's device work (waited by spinning)
@@ -1676,7 +1890,7 @@ int wait_stream(SearchCtx* c, hipStream_t s) {
 void ctx_free_all(SearchCtx* c) {
   for (DevBuf* b : {&c->qin, &c->q32, &c->qn, &c->q16, &c->part_s, &c->part_i, &c->thresh, &c->fail_list,
                     &c->counters, &c->cand_cnt, &c->cand, &c->scratch, &c->out_s, &c->out_s64, &c->out_r,
-                    &c->theta, &c->part_tau})
+                    &c->theta, &c->part_tau, &c->rec})
     release(*b);
   mrag_knn::release(c->gws);
   if (c->host_counters) (void)hipHostFree(c->host_counters);
@@ -2014,8 +2228,18 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
     S = std::min(S, ntiles);
     S = std::min(S, MAX_MERGE_ENTRIES / KL);
     if (S >= 8) S &= ~7;
+    // Sample pass (v3, 256-query groups, when every split has >= 4 * stride tiles): seed only, or
+    // counting (its rows reach K8 through XLISTS extra lists) while the group ids fit the record
+    const int min_tiles = ntiles / S;
+    const int stride = sample_stride_for(k);
+    const bool sampled = use_v3 && qb == 4 && min_tiles >= 4 * stride;
+    const int max_sample_tiles = ((ntiles + S - 1) / S + stride - 1) / stride;
+    int idbits = 2;
+    while ((1 << idbits) < 4 * max_sample_tiles) ++idbits;
+    const bool counting = sampled && counting_sample_for(k) && idbits <= REC_ID_BITS_MAX;
+    const int SX = counting ? XLISTS : 0;
     const int M = std::min<int>(k + 32, S * KL);
-    const int R = (int)next_pow2((int64_t)S * KL);
+    const int R = (int)next_pow2((int64_t)(S + SX) * KL);
     const int Mp = (int)next_pow2(std::max(M, 2));
     info[0] = S;
     info[1] = (int32_t)Qp;
@@ -2030,15 +2254,17 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
     if (int rc = ensure(c->q32, (size_t)Qp * DP * 4)) return rc;
     if (int rc = ensure(c->qn, (size_t)Qp * 8)) return rc;
     if (int rc = ensure(c->q16, (size_t)Qp * DP * 2)) return rc;
-    if (int rc = ensure(c->part_s, (size_t)S * Qp * KL * 4)) return rc;
-    if (int rc = ensure(c->part_i, (size_t)S * Qp * KL * 4)) return rc;
+    if (int rc = ensure(c->part_s, (size_t)(S + SX) * Qp * KL * 4)) return rc;
+    if (int rc = ensure(c->part_i, (size_t)(S + SX) * Qp * KL * 4)) return rc;
     if (int rc = ensure(c->thresh, (size_t)Qp * 4)) return rc;
     if (int rc = ensure(c->fail_list, (size_t)Qp * 4)) return rc;
     if (int rc = ensure(c->counters, 16)) return rc;
     if (int rc = ensure(c->cand_cnt, (size_t)Qp * 4)) return rc;
     if (int rc = ensure(c->theta, (size_t)Qp * 4)) return rc;
     if (use_v3)
-      if (int rc = ensure(c->part_tau, (size_t)S * Qp * 4)) return rc;
+      if (int rc = ensure(c->part_tau, (size_t)(S + SX) * Qp * 4)) return rc;
+    if (counting)
+      if (int rc = ensure(c->rec, (size_t)S * Qp * 16 * 4)) return rc;
 
     if (int rc = launch_prep(qsrc, nq, D, DP, Qp, (float*)c->q32.p, (double*)c->qn.p, (_Float16*)c->q16.p, s,
                              PrepClear{(int32_t*)c->counters.p, (int32_t*)c->cand_cnt.p, (uint32_t*)c->theta.p}))
@@ -2064,7 +2290,7 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
     sp.k = k;
     sp.part_tau = use_v3 ? (float*)c->part_tau.p : nullptr;
 
-    const scan_fn scan = use_v3 ? get_scan3(DP, false, qb) : get_scan(DP, KL, false);
+    const scan_fn scan = use_v3 ? get_scan3(DP, 0, qb) : get_scan(DP, KL, false);
     const scan_fn collect = get_scan(DP, 8, true);
     if (!scan || !collect) return mrag::fail(MRAG_ERR_UNSUPPORTED, "no scan kernel for DP=%d", DP);
     const dim3 sgrid((unsigned)(qgroups * S));
@@ -2074,15 +2300,41 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
     // slower in the main scan); stride 16 (32: +5 %, 64: +14 %, none: +70 % scan time). K7s
     // (qb == 1) streams at the HBM rate, where the pre-pass costs more than the inserts it saves
     // (Q = 1: 0.270 -> 0.247 ms without it, notes/knn_scan_experiments.md).
-    const int min_tiles = ntiles / S;
-    const int stride = sample_stride_for(k);
-    if (use_v3 && qb == 4 && min_tiles >= 4 * stride) {
-      sp.sample_stride = stride;
+    // The counting pass (k <= 16) keeps a per-lane record instead of the maxima; the resolve
+    // kernel seeds the threshold from it and lists the sampled rows above the seed, and the main
+    // scan walks the other tiles only.
+    sp.sample_stride = stride;  // MODE 0 reads it too (skip_sampled)
+    if (sampled) {
       sp.sample_tiles = min_tiles / stride;
-      hipLaunchKernelGGL(get_scan3(DP, true, qb), sgrid, dim3(SCAN2_THREADS), 0, s, sp);
+      if (counting) {
+        sp.rec = (uint32_t*)c->rec.p;
+        sp.rec_keep = ~((1u << idbits) - 1u);
+      }
+      hipLaunchKernelGGL(get_scan3(DP, counting ? 2 : 1, qb), sgrid, dim3(SCAN2_THREADS), 0, s, sp);
       MRAG_CHECK_LAUNCH();
-      hipLaunchKernelGGL(theta_init_kernel, dim3((unsigned)nq), dim3(64), 0, s, (const float*)sp.part_s, 4 * S,
-                         (int)Qp, k, sp.theta);
+      if (counting) {
+        ResolveParams rp{};
+        rp.rec = sp.rec;
+        rp.idmask = ~sp.rec_keep;
+        rp.splits = S;
+        rp.Qp = (int)Qp;
+        rp.k = k;
+        rp.DP = DP;
+        rp.tile_step = S * stride;
+        rp.label_filter = label_filter;
+        rp.x16 = sp.x16;
+        rp.q16 = sp.q16;
+        rp.labels = sp.labels;
+        rp.theta = sp.theta;
+        rp.part_s = sp.part_s;
+        rp.part_i = sp.part_i;
+        rp.part_tau = sp.part_tau;
+        hipLaunchKernelGGL(sample_resolve_kernel, dim3((unsigned)nq), dim3(64), 0, s, rp);
+        sp.skip_magic = (uint32_t)((1ull << 32) / (uint64_t)(stride - 1) + 1);
+      } else {
+        hipLaunchKernelGGL(theta_init_kernel, dim3((unsigned)nq), dim3(64), 0, s, (const float*)sp.part_s, 4 * S,
+                           (int)Qp, k, sp.theta);
+      }
       MRAG_CHECK_LAUNCH();
     }
     if (profile) MRAG_HIP(hipEventRecord(c->ev0, s));
@@ -2093,7 +2345,8 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
     MergeParams mp{};
     mp.part_s = sp.part_s;
     mp.part_i = sp.part_i;
-    mp.splits = S;
+    mp.splits = S + SX;
+    mp.scan_splits = S;
     mp.KL = KL;
     mp.Qp = (int)Qp;
     mp.nq = (int)nq;
