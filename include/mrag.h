@@ -290,7 +290,8 @@ int mrag_hash_tokenize(const char* const* texts, const int64_t* lens, int32_t n,
 
 /* K3 building block: C[M][N] (op)= A[M][K] . W[N][K]^T + bias (device pointers;
  * A, W fp16 row-major; epilogue 0 f16 out, 1 f16 quick_gelu, 2 f16 gelu_erf,
- * 3 f32 C += , 4 f32 out). N % 128 == 0, K % 64 == 0; bias and C 16-byte aligned. */
+ * 3 f32 C += , 4 f32 out). N % 128 == 0, K % 64 == 0; bias and C 16-byte aligned. bias may be
+ * NULL (zeros): the ViT patch embedding and both CLIP projections have none. */
 int mrag_gemm_nt(const void* A, const void* W, const float* bias, void* C, int32_t M, int32_t N, int32_t K,
                  int32_t epilogue, void* stream);
 /* The same with the kernel chosen: 0 the automatic rule, 1 K3 (128 x 128 tiles), 2 K3d (persistent
@@ -299,6 +300,12 @@ int mrag_gemm_nt(const void* A, const void* W, const float* bias, void* C, int32
  * exists for per-kernel timing and the bit-identity tests. */
 int mrag_gemm_nt_kernel(const void* A, const void* W, const float* bias, void* C, int32_t M, int32_t N, int32_t K,
                         int32_t epilogue, int32_t kernel, void* stream);
+/* The same with explicit row strides in elements: A rows lda apart (lda >= K, lda % 8 == 0; the
+ * cross-encoder pooler reads token 0 of every sequence with lda = T * hidden), C rows ldc apart
+ * (ldc >= N, ldc % 4 == 0). K3d addresses A and W with 32-bit element offsets: forced, it is rejected
+ * once (M - 1) * lda + K or (N - 1) * K + K exceeds INT_MAX; the automatic rule takes K3 there. */
+int mrag_gemm_nt_ld(const void* A, int32_t lda, const void* W, const float* bias, void* C, int32_t ldc, int32_t M,
+                    int32_t N, int32_t K, int32_t epilogue, int32_t kernel, void* stream);
 
 /* ---- building blocks: tests and timing -------------------------------------------------
  * One launch of one encoder kernel each, on device pointers and a stream (NULL: the default

@@ -47,6 +47,7 @@ def _register_signatures():
         "mrag_encoder_embed_tokens": [vp, vp, vp, i32, i32, vp, i32, i32, vp],
         "mrag_gemm_nt": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
         "mrag_gemm_nt_kernel": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+        "mrag_gemm_nt_ld": [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
         "mrag_encoder_score_pairs": [vp, vp, vp, vp, i32, i32, vp, i32, vp],
         # building blocks (tests and timing)
         "mrag_layernorm": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp],
@@ -63,7 +64,7 @@ def _register_signatures():
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            if name == "mrag_gemm_nt_kernel":  # timing / test entry, absent from older builds (A/B)
+            if name in ("mrag_gemm_nt_kernel", "mrag_gemm_nt_ld"):  # timing / test entries, absent from older builds (A/B)
                 continue
             raise
         fn.restype = ctypes.c_int32
@@ -190,9 +191,13 @@ class GpuEncoder:
 GEMM_KERNELS = {"auto": 0, "k3": 1, "k3d": 2, "k3s": 3, "k3w": 4}
 
 
-def gemm_nt(A, W, bias, C, epilogue: int, kernel: str = "auto"):
+def gemm_nt(A, W, bias, C, epilogue: int, kernel: str = "auto", lda: Optional[int] = None,
+            ldc: Optional[int] = None):
     """The encoder GEMM on torch CUDA tensors (test / building-block entry): the automatic kernel
-    choice of the towers, or one kernel forced (``GEMM_KERNELS``: bit-identity tests, timing)."""
+    choice of the towers, or one kernel forced (``GEMM_KERNELS``: bit-identity tests, timing).
+    With ``lda`` / ``ldc`` (row strides in elements, default K / N) the operands are read from
+    ``A.data_ptr()`` / written at ``C.data_ptr()`` with those strides (``A`` and ``C`` still give
+    M, K and the base addresses: pass views of the strided buffers)."""
     import torch
 
     lib = _register_signatures()
@@ -200,7 +205,11 @@ def gemm_nt(A, W, bias, C, epilogue: int, kernel: str = "auto"):
     N = W.shape[0]
     stream = torch.cuda.current_stream(A.device).cuda_stream
     bp = bias.data_ptr() if bias is not None else None
-    if kernel == "auto":
+    if lda is not None or ldc is not None:
+        _native.check(lib.mrag_gemm_nt_ld(A.data_ptr(), K if lda is None else lda, W.data_ptr(), bp, C.data_ptr(),
+                                          N if ldc is None else ldc, M, N, K, epilogue, GEMM_KERNELS[kernel], stream),
+                      "mrag_gemm_nt_ld")
+    elif kernel == "auto":
         _native.check(lib.mrag_gemm_nt(A.data_ptr(), W.data_ptr(), bp, C.data_ptr(), M, N, K, epilogue, stream),
                       "mrag_gemm_nt")
     else:

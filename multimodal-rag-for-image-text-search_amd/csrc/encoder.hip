@@ -962,6 +962,26 @@ int mrag_gemm_nt_kernel(const void* A, const void* W, const float* bias, void* C
   return launch_gemm(g, epilogue, (hipStream_t)stream, kernel);
 }
 
+int mrag_gemm_nt_ld(const void* A, int32_t lda, const void* W, const float* bias, void* C, int32_t ldc, int32_t M,
+                    int32_t N, int32_t K, int32_t epilogue, int32_t kernel, void* stream) {
+  MRAG_REQUIRE(A && W && C, "NULL pointer");
+  MRAG_REQUIRE(M >= 0 && N > 0 && K > 0, "bad shape");
+  MRAG_REQUIRE(lda >= K && ldc >= N, "lda=%d < K=%d or ldc=%d < N=%d", lda, K, ldc, N);
+  MRAG_REQUIRE(kernel >= GEMM_AUTO && kernel <= GEMM_K3W, "bad kernel %d", kernel);
+  GemmArgs g{};
+  g.A = (const _Float16*)A;
+  g.W = (const _Float16*)W;
+  g.bias = bias;
+  g.C = C;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.lda = lda;
+  g.ldw = K;
+  g.ldc = ldc;
+  return launch_gemm(g, epilogue, (hipStream_t)stream, kernel);
+}
+
 // ---- building blocks: the other encoder kernels, one launch each (tests and timing) ----------
 // device pointers and a stream; no allocation, no sync
 

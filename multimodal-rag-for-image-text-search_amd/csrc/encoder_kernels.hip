@@ -11,6 +11,7 @@
 // input is f16 (LayerNorm writes the f16 copy), weights are f16 [out][in] (torch Linear
 // layout, K contiguous for both GEMM operands), biases / LN params / embeddings f32.
 #include <algorithm>
+#include <climits>
 #include <type_traits>
 #include <cstdlib>
 
@@ -542,6 +543,8 @@ __global__ __launch_bounds__(G8_THREADS) void gemm_8p_kernel(GemmArgs g) {
   // offsets once per tile (no per-phase division or slot selection).
   int ld_kt, ld_ke, ld_T, ld_seg = 0, ld_par = 0;
   seg(0, ld_T, ld_kt, ld_ke);
+  // int on purpose (registers of the hottest kernel): launch_gemm admits K3d only while
+  // (M - 1) * lda + K and (N - 1) * ldw + K fit an int (k3d_offsets_fit), larger shapes take K3
   int gA[2][PA], gB[2][PB];  // element offsets (row * ld + chunk) for the tile being loaded
   auto load_tile_offsets = [&]() {
     const int tm = ld_T / tiles_n;
@@ -1685,9 +1688,17 @@ int launch_gemm(const GemmArgs& g, int epi, hipStream_t s, int kernel) {
   MRAG_REQUIRE(g.lda % 8 == 0 && g.ldw % 8 == 0 && g.ldc % 4 == 0, "gemm: lda/ldw must be multiples of 8, ldc of 4");
   MRAG_REQUIRE(((uintptr_t)g.bias & 15) == 0 && ((uintptr_t)g.C & 15) == 0, "gemm: bias and C must be 16-byte aligned");
   if (kernel == GEMM_K3W || (kernel == GEMM_AUTO && gemm_ws_auto(g, epi))) return launch_gemm_ws(g, epi, s);
+  // K3d keeps its source element offsets (gA / gB in gemm_8p_kernel) as int: it is eligible only
+  // while the last element of A and of W is within INT_MAX of the base (K = 3072: M < 699,051).
+  // Past that the automatic rule takes K3, whose offsets are size_t. No HIP call before this.
+  const bool k3d_offsets_fit = (int64_t)(g.M - 1) * g.lda + g.K <= (int64_t)INT_MAX &&
+                               (int64_t)(g.N - 1) * g.ldw + g.K <= (int64_t)INT_MAX;
   if (kernel == GEMM_K3D) {
     MRAG_REQUIRE(g.M >= 1024 && g.N <= G8_BIAS_MAX && g.N % 256 == 0, "gemm K3d: shape M=%d N=%d unsupported", g.M,
                  g.N);
+    MRAG_REQUIRE(k3d_offsets_fit,
+                 "gemm K3d: source offset (M-1)*lda+K or (N-1)*ldw+K exceeds a 32-bit int (M=%d lda=%d N=%d ldw=%d K=%d)",
+                 g.M, g.lda, g.N, g.ldw, g.K);
     const int ntiles = ((g.M + G8Geom::BM - 1) / G8Geom::BM) * (g.N / G8Geom::BN);
     const int nb = std::min((ntiles + 7) / 8 * 8, std::max(8, num_cus() / 8 * 8));
     return launch_epi<K3dKern>(epi, dim3((unsigned)nb), dim3(G8_THREADS), s, g);
@@ -1695,7 +1706,8 @@ int launch_gemm(const GemmArgs& g, int epi, hipStream_t s, int kernel) {
   if (kernel == GEMM_K3S) {
     MRAG_REQUIRE(g.M <= 64, "gemm K3s: M=%d > 64", g.M);
   }
-  if (kernel == GEMM_AUTO && g.M >= 1024 && g.N <= G8_BIAS_MAX && g.N % 256 == 0 && !k3_beats_k3d(g)) {
+  if (kernel == GEMM_AUTO && g.M >= 1024 && g.N <= G8_BIAS_MAX && g.N % 256 == 0 && k3d_offsets_fit &&
+      !k3_beats_k3d(g)) {
     const int ntiles = ((g.M + G8Geom::BM - 1) / G8Geom::BM) * (g.N / G8Geom::BN);
     const int nb = std::min((ntiles + 7) / 8 * 8, std::max(8, num_cus() / 8 * 8));
     return launch_epi<K3dKern>(epi, dim3((unsigned)nb), dim3(G8_THREADS), s, g);

@@ -263,3 +263,95 @@ def cls_head_ref(pooled, Wc, bc):
     """float64 logits and the magnitude sum |tanh| |W| + |b| their f32 error scales with."""
     t = torch.tanh(pooled.double())
     return t @ Wc.double().t() + bc.double(), t.abs() @ Wc.double().abs().t() + bc.double().abs()
+
+
+# ---------------------------------------------------------------------------------------
+# GEMM (K3 / K3s / K3d / K3w): C = epilogue(A W^T + bias)
+
+GEMM_QUICK_GELU, GEMM_GELU_ERF, GEMM_RESIDUAL = 1, 2, 3  # epilogue 0: f16 out, 4: f32 out
+
+
+def gemm_act_ref(x, epi: int):
+    """float64 activation of epilogue `epi`: quick-GELU x sigmoid(1.702 x) (1), exact-erf GELU (2),
+    the identity otherwise."""
+    if epi == GEMM_QUICK_GELU:
+        return x * torch.sigmoid(1.702 * x)
+    if epi == GEMM_GELU_ERF:
+        return 0.5 * x * (1.0 + torch.erf(x * (1.0 / math.sqrt(2.0))))
+    return x
+
+
+def gemm_ref(A, W, bias, epi: int, C0=None):
+    """float64 reference of one GEMM launch on the inputs' device.
+
+    Returns (ref, x, S): x = A W^T + bias, the pre-activation; ref = act(x) (+ C0 for epilogue 3);
+    S = |A| |W|^T + |bias| (+ |C0|), the magnitude the f32 rounding error scales with."""
+    Ad, Wd = A.double(), W.double()
+    x = Ad @ Wd.t()
+    S = Ad.abs() @ Wd.abs().t()
+    if bias is not None:
+        x = x + bias.double()
+        S = S + bias.double().abs()
+    ref = gemm_act_ref(x, epi)
+    if epi == GEMM_RESIDUAL:
+        ref = ref + C0.double()
+        S = S + C0.double().abs()
+    return ref, x, S
+
+
+def gemm_int_operands(M: int, N: int, K: int, seed: int, device=None):
+    """A [M][K], W [N][K] fp16 integers uniform in [-4, 4], bias [N] f32 integers in [-64, 64],
+    C0 [M][N] f32 integers in [-1000, 1000].
+
+    Every product is an integer of magnitude <= 16 and every partial sum, in any order, with the
+    bias and C0, an integer of magnitude <= 16 K + 64 + 1000 (50,216 at K = 3072) < 2^24: the f32
+    result is exact whatever the accumulation order, and, below 65504, the f16 result is the
+    round-to-nearest-even fp16 of the exact integer."""
+    g = torch.Generator(device=device or "cpu").manual_seed(seed)
+    kw = dict(generator=g, device=device or "cpu")
+    A = torch.randint(-4, 5, (M, K), **kw).half()
+    W = torch.randint(-4, 5, (N, K), **kw).half()
+    bias = torch.randint(-64, 65, (N,), **kw).float()
+    C0 = torch.randint(-1000, 1001, (M, N), **kw).float()
+    return A, W, bias, C0
+
+
+GEMM_KINDS = ("plain", "cancel")
+
+
+def gemm_real_operands(kind: str, M: int, N: int, K: int, seed: int, device=None):
+    """fp16 A [M][K], W [N][K], f32 bias [N], f32 C0 [M][N] ~ N(0, 1).
+
+    plain:  A ~ N(0, 1) with four columns scaled by 30 (the outlier features a LayerNorm output
+            carries), W ~ 0.05 N, bias ~ 0.1 N.
+    cancel: the second half of every W row is the negated first half, the second half of every A
+            row the first half times (1 + 2^-9) (rounded to fp16): the two halves of every dot
+            product cancel to ~2^-10 of their size, so |x| << S and an error that a max-norm
+            comparison hides under the largest element is visible per element. bias ~ 0.01 N
+            (the plain kind's 0.1 N would be the whole of x at K = 64)."""
+    g = torch.Generator(device=device or "cpu").manual_seed(seed)
+    kw = dict(generator=g, device=device or "cpu")
+    A = torch.randn(M, K, **kw)
+    W = torch.randn(N, K, **kw) * 0.05
+    bias = torch.randn(N, **kw) * 0.1
+    C0 = torch.randn(M, N, **kw)
+    if kind == "plain":
+        cols = torch.randperm(K, **kw)[:4]
+        A[:, cols] *= 30.0
+    elif kind == "cancel":
+        h = K // 2
+        W[:, h:] = -W[:, :h]
+        A = A.half().float()
+        A[:, h:] = A[:, :h] * (1.0 + 2.0 ** -9)
+        bias = bias * 0.1
+    else:
+        raise ValueError(kind)
+    return A.half().contiguous(), W.half().contiguous(), bias.contiguous(), C0.contiguous()
+
+
+def gemm_acc_bound(S, K: int):
+    """|acc - x| allowed for the f32 accumulator: (K + K / 32 + 2) 2^-23 S. The K products are exact
+    in f32 (fp16 x fp16 has 22 significant bits); summing them, the K / 32 chunk results and the
+    bias in any order rounds at most K + K / 32 + 1 times, each by at most one ulp (2^-23 relative,
+    whatever the rounding mode) of a partial sum of magnitude <= S (1 + small)."""
+    return (K + K / 32 + 2) * 2.0 ** -23 * S

@@ -3,7 +3,8 @@ entries of the C ABI (mrag_attention, mrag_layernorm, ...), each against a plain
 reference of the same operation (tests/_kernel_refs.py, itself checked on the CPU by
 tests/test_kernel_refs_cpu.py) at the shapes, masks and value ranges where such kernels go
 wrong. The towers reach these kernels only at their own shapes, on synthetic weights (flat
-softmax), through a 1e-4 cosine after 6-12 layers.
+softmax), through a 1e-4 cosine after 6-12 layers. The GEMM kernels have the same kind of tests
+in tests/test_gemm_kernels_gpu.py.
 
 Every launch is tiny; the references run in float64 on the GPU next to the kernels.
 """

@@ -228,7 +228,7 @@ def test_gemm_shapes_every_epilogue(cuda):
             assert torch.equal(outs[0], outs[1]), ("nondeterministic", M, N, K, epi)
             err = (C.float() - r).abs().max().item() / r.abs().max().item()
             assert err < (2e-3 if epi <= 2 else 2e-5), (M, N, K, epi, err)
-    # bias == NULL (no tower passes it): K3 and K3d forced, an f16 and an f32 epilogue, against A W^T
+    # bias == NULL (the ViT patch embedding and both CLIP projections): K3 and K3d forced, an f16 and an f32 epilogue, against A W^T
     for kern, (M, N, K) in (("k3", (300, 256, 64)), ("k3d", (1100, 768, 768))):
         g = torch.Generator(device="cuda").manual_seed(K)
         A = (torch.randn(M, K, generator=g, device="cuda") * 0.5).half()
@@ -310,7 +310,7 @@ def test_gemm_weight_stationary_equals_k3(cuda, N, K):
     M: clamped loads, no stores), and small enough that some row ranges own no tile or one tile;
     and within K3's tolerance of a torch fp32 product. The automatic rule takes K3w for these
     shapes at M >= 4096. (1152, 512) and (384, 512) are K = 512 with N % 192 == 0 only: three
-    64-column blocks per wave at the 16-step K. Without a bias (no tower passes NULL): the same
+    64-column blocks per wave at the 16-step K. Without a bias (as the CLIP projections call it): the same
     checks at one K = 384 and one K = 512 shape."""
     import torch
 

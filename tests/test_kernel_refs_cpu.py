@@ -220,6 +220,69 @@ def test_small_op_refs():
     assert bool((mag >= logits.abs() - 1e-12).all())
 
 
+def test_gemm_ref_matches_torch():
+    """gemm_ref == torch's linear / gelu / x sigmoid(1.702 x) in float64; S bounds |x|."""
+    for kind in R.GEMM_KINDS:
+        A, W, bias, C0 = R.gemm_real_operands(kind, 37, 128, 192, seed=3)
+        for b in (bias, None):
+            lin = torch.nn.functional.linear(A.double(), W.double(), b.double() if b is not None else None)
+            for epi in range(5):
+                ref, x, S = R.gemm_ref(A, W, b, epi, C0)
+                torch.testing.assert_close(x, lin, rtol=1e-12, atol=1e-12)
+                exp = {1: lin * torch.sigmoid(1.702 * lin), 2: torch.nn.functional.gelu(lin),
+                       3: lin + C0.double()}.get(epi, lin)
+                torch.testing.assert_close(ref, exp, rtol=1e-12, atol=1e-12)
+                mag = A.double().abs() @ W.double().abs().t() + (b.double().abs() if b is not None else 0.0)
+                torch.testing.assert_close(S, mag + (C0.double().abs() if epi == 3 else 0.0), rtol=1e-12, atol=1e-12)
+                assert bool((S >= x.abs() - 1e-12).all())
+
+
+def test_gemm_int_operands_are_exact():
+    """The integer generator at the largest K any GEMM test uses (3072): every partial sum below
+    2^24 (f32 exact in any order), the result below the fp16 maximum, and the fp16 rounding of
+    integers up to 2048 the identity."""
+    A, W, bias, C0 = R.gemm_int_operands(65, 128, 3072, seed=1)
+    for t, lo, hi in ((A, -4, 4), (W, -4, 4), (bias, -64, 64), (C0, -1000, 1000)):
+        assert float(t.min()) >= lo and float(t.max()) <= hi and bool((t.double() == t.double().round()).all())
+    assert A.dtype == torch.float16 and W.dtype == torch.float16 and bias.dtype == torch.float32
+    assert sorted(set(A.flatten().tolist())) == [float(v) for v in range(-4, 5)]
+    for epi in (0, 3, 4):
+        ref, x, S = R.gemm_ref(A, W, bias, epi, C0)
+        assert float(S.max()) < 2 ** 24
+        assert float(x.abs().max()) < 65504
+        assert bool((ref == ref.round()).all())
+        small = ref.abs() <= 2048
+        assert bool(small.any()) and torch.equal(ref.half().double()[small], ref[small])
+        assert torch.equal(ref.float().double(), ref)
+    assert 16 * 3072 + 64 + 1000 < 2 ** 24
+
+
+def test_gemm_cancel_operands_cancel():
+    """cancel: the median |x| / S is below 1e-2 at every K the GPU tests use (plain: it is not)."""
+    for K in (64, 192, 384, 512, 704, 768):
+        A, W, bias, C0 = R.gemm_real_operands("cancel", 64, 128, K, seed=K)
+        _, x, S = R.gemm_ref(A, W, bias, 4)
+        assert float((x.abs() / S).median()) < 1e-2, K
+        h = K // 2
+        assert torch.equal(W[:, h:], -W[:, :h])
+        A, W, bias, C0 = R.gemm_real_operands("plain", 64, 128, K, seed=K)
+        _, x, S = R.gemm_ref(A, W, bias, 4)
+        assert float((x.abs() / S).median()) > 3e-2, K
+        assert int((A.float().abs().amax(0) > 40).sum()) == 4  # the four outlier columns
+
+
+def test_gemm_activation_slopes():
+    """|d act / dx| < 1.13 for both activations on [-20, 20] (the factor on the accumulation bound
+    of epilogues 1 and 2 in tests/test_gemm_kernels_gpu.py)."""
+    x = torch.linspace(-20, 20, 4_000_001, dtype=torch.float64)
+    for epi in (1, 2):
+        y = R.gemm_act_ref(x, epi)
+        slope = ((y[1:] - y[:-1]) / (x[1:] - x[:-1])).abs()
+        assert 1.0 < float(slope.max()) < 1.13, (epi, float(slope.max()))
+    b = R.gemm_acc_bound(torch.tensor(1.0, dtype=torch.float64), 64)
+    assert float(b) == (64 + 2 + 2) * 2.0 ** -23
+
+
 def test_building_block_argument_checks():
     """The rejections that need no GPU: they return MRAG_ERR_ARG before any HIP call (the pointers
     are never dereferenced on the host)."""
@@ -250,3 +313,39 @@ def test_building_block_argument_checks():
     assert lib.mrag_vit_im2col(p, p, 1, 64, 12, None) == ERR_ARG
     assert lib.mrag_vit_embed_ln(p, p, p, p, p, p, 1, 2, 6, 1e-5, None) == ERR_ARG
     assert lib.mrag_token_embed(p, p, p, None, None, p, 1, 2, 6, 10, None) == ERR_ARG
+
+    # ---- GEMM: kernel ids as app.encoders.GEMM_KERNELS
+    AUTO, K3, K3D, K3S, K3W = range(5)
+
+    def gemm(M, N, K, epi=0, kernel=AUTO, A=p, W=p, bias=p, C=p):
+        return lib.mrag_gemm_nt_kernel(A, W, bias, C, M, N, K, epi, kernel, None)
+
+    def gemm_ld(M, N, K, lda, ldc, epi=0, kernel=AUTO):
+        return lib.mrag_gemm_nt_ld(p, lda, p, p, p, ldc, M, N, K, epi, kernel, None)
+
+    # K3d keeps 32-bit source offsets: (M - 1) * lda + K > INT_MAX is rejected when it is forced (the
+    # ViT fc2 / patch-embedding K at ~14,000 images), one row less passes this check (and fails later,
+    # at the launch, on a machine without a GPU: not called here)
+    assert (699_051 - 1) * 3072 + 3072 > 2 ** 31 - 1 >= (699_050 - 1) * 3072 + 3072
+    assert gemm(699_051, 256, 3072, kernel=K3D) == ERR_ARG
+    assert b"offset" in lib.mrag_last_error()
+    assert gemm_ld(1100, 256, 64, 1_999_992, 256, kernel=K3D) == ERR_ARG  # the same through lda
+    assert b"offset" in lib.mrag_last_error()
+    # shape rules of every kernel
+    assert gemm(128, 192, 64) == ERR_ARG and gemm(128, 128, 96) == ERR_ARG
+    assert lib.mrag_gemm_nt(p, p, p, p, 128, 192, 64, 0, None) == ERR_ARG
+    assert gemm(128, 128, 64, bias=p + 8) == ERR_ARG and b"aligned" in lib.mrag_last_error()
+    assert gemm(128, 128, 64, C=p + 8) == ERR_ARG and b"aligned" in lib.mrag_last_error()
+    assert gemm(128, 128, 64, A=None) == ERR_ARG and gemm(128, 128, 64, kernel=5) == ERR_ARG
+    assert gemm(128, 128, 64, epi=5, kernel=K3W) == ERR_ARG
+    for shape in ((1023, 256, 64), (1024, 384, 64), (1024, 4352, 64)):
+        assert gemm(*shape, kernel=K3D) == ERR_ARG and b"K3d" in lib.mrag_last_error(), shape
+    assert gemm(65, 128, 64, kernel=K3S) == ERR_ARG and b"K3s" in lib.mrag_last_error()
+    for shape, epi in (((4096, 256, 512), 4), ((4096, 256, 512), 3), ((4096, 256, 256), 0), ((4095, 256, 512), 0),
+                       ((4096, 128, 512), 0)):
+        assert gemm(*shape, epi=epi, kernel=K3W) == ERR_ARG and b"K3w" in lib.mrag_last_error(), (shape, epi)
+    # explicit strides: at least a row, and the vector widths of the loads / stores
+    assert gemm_ld(128, 128, 64, 56, 128) == ERR_ARG and b"lda" in lib.mrag_last_error()
+    assert gemm_ld(128, 128, 64, 64, 124) == ERR_ARG and b"ldc" in lib.mrag_last_error()
+    assert gemm_ld(128, 128, 64, 68, 128) == ERR_ARG and gemm_ld(128, 128, 64, 64, 130) == ERR_ARG
+    assert gemm_ld(128, 128, 64, 64, 128, kernel=7) == ERR_ARG
