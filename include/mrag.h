@@ -171,15 +171,19 @@ int mrag_fuse_scores(const float* text_scores, int32_t kt, const float* image_sc
 
 typedef struct mrag_encoder_config {
   int32_t kind;           /* MRAG_ENC_*                                            */
-  int32_t hidden;         /* 768 (ViT-B/32), 512 (CLIP text), 384 (MiniLM-L6)      */
-  int32_t layers;         /* 12, 12, 6                                             */
+  int32_t hidden;         /* 768 (ViT-B/32), 512 (CLIP text), 384 (MiniLM-L6); a multiple of 128, <= 1024
+                             (ViT-L/14: 1024), hidden / heads 32 or 64               */
+  int32_t layers;         /* 12, 12, 6 (1..64; ViT-L/14: 24)                       */
   int32_t heads;          /* 12, 8, 12                                             */
-  int32_t intermediate;   /* 3072, 2048, 1536                                      */
+  int32_t intermediate;   /* 3072, 2048, 1536 (a multiple of 128)                  */
   int32_t max_positions;  /* text: 77 / 512; vision: unused                        */
   int32_t vocab;          /* text: 49408 / 30522                                   */
-  int32_t proj_dim;       /* CLIP: 512; BERT: unused; BERT_PAIR: num_labels (1)    */
-  int32_t image_size;     /* vision: 224                                           */
-  int32_t patch_size;     /* vision: 32                                            */
+  int32_t proj_dim;       /* CLIP: 512 (a multiple of 128; ViT-L/14: 768); BERT: unused;
+                             BERT_PAIR: num_labels (1)                              */
+  int32_t image_size;     /* vision: 224; a multiple of patch_size with
+                             (image_size / patch_size)^2 + 1 <= 512 tokens         */
+  int32_t patch_size;     /* vision: 32, 16, 14, ... (any >= 1; the patch weight is set as
+                             [hidden][3][P][P] and packed with rows padded to a multiple of 64) */
   int32_t act;            /* 0 = quick_gelu (CLIP), 1 = gelu (erf, BERT)          */
   int32_t eos_token_id;   /* CLIP text pooling: first id == eos (>= 0) or argmax(ids) (-1) */
   float ln_eps;           /* 1e-5 (CLIP), 1e-12 (BERT)                             */
@@ -321,13 +325,18 @@ int mrag_layernorm(const float* x, const int32_t* gather, float* y32, void* y16,
 /* K4 attention: out[B*L][H*head_dim] (fp16) = softmax(scale * q k^T) v per (sequence, head) from
  * qkv[B*L][3*H*head_dim] (fp16, q | k | v); mask[B][L] (1 = keep the key) or NULL; causal != 0
  * keeps key <= query. Query rows without a valid key give zeros. L in 1..512, head_dim 32 or 64.
- * kernel: 0 the towers' rule (seq64 for 33 <= L <= 64, flash16 otherwise), 1 flash16, 2 seq64
- * (rejected unless 33 <= L <= 64). Both kernels give the same bytes. */
+ * kernel: 0 the towers' rule (seq64 for 33 <= L <= 64, seqkv for 65 <= L <= 320, flash16
+ * otherwise), 1 flash16, 2 seq64 (rejected unless 33 <= L <= 64), 3 seqkv (one workgroup per
+ * (sequence, head) with K and V staged once in LDS; rejected unless 65 <= L <= 320). Every kernel
+ * gives the same bytes. */
 int mrag_attention(const void* qkv, void* out, const int32_t* mask, int32_t B, int32_t L, int32_t H, int32_t head_dim,
                    int32_t causal, float scale, int32_t kernel, void* stream);
-/* K1 prologue: CLIP pixel normalisation + patch im2col. img[B][S][S][3] u8 -> out[B*(S/P)^2][3*P*P]
- * fp16, K ordered (c, kh, kw). P % 8 == 0, S % P == 0; P = 32 with S % 16 == 0 and a 16-byte
- * aligned img takes the vectorised kernel (the same bytes). */
+/* K1 prologue: CLIP pixel normalisation + patch im2col. img[B][S][S][3] u8 -> out[B*(S/P)^2][Kpad]
+ * fp16, K ordered (c, kh, kw). Any P >= 1 with S % P == 0. For P % 8 == 0, Kpad = 3*P*P; P = 32
+ * with S % 16 == 0 and a 16-byte aligned img takes the vectorised kernel (the same bytes). For any
+ * other P (ViT-L/14) the rows are padded to Kpad = 3*P*P rounded up to a multiple of 64 halves
+ * (P = 14: 588 -> 640) and columns 3*P*P .. Kpad-1 are written as +0 on every launch. out is
+ * 16-byte aligned and holds B*(S/P)^2 * Kpad halves. */
 int mrag_vit_im2col(const uint8_t* img, void* out, int32_t B, int32_t S, int32_t P, void* stream);
 /* ViT token assembly + pre-LN: X[b*T + t] = LN((t == 0 ? cls : patch[b*(T-1) + t-1]) + pos[t]), f32,
  * D % 4 == 0, D <= 1024. */

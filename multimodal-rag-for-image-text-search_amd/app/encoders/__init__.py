@@ -1,4 +1,5 @@
-"""GPU encoders: CLIP ViT-B/32 image tower, CLIP text tower, MiniLM-L6 — through the
+"""GPU encoders: CLIP image towers (ViT-B/32, B/16, L/14 at 224 pixels), CLIP text towers,
+BERT sentence encoders (MiniLM-L6 / L12) and cross-encoders — through the
 C ABI (``mrag_encoder_*`` in include/mrag.h, kernels in csrc/encoder*.hip).
 
 Replaces the model calls of the reference's ``app/ml/embeddings.py``:
@@ -19,10 +20,16 @@ import numpy as np
 from app import _native
 from app.encoders.weights import (
     CLIP_TEXT_B32,
+    CLIP_TEXT_L14,
+    CLIP_VISION_B16,
     CLIP_VISION_B32,
+    CLIP_VISION_L14,
     MINILM_L6,
     MSMARCO_MINILM_L6_CE,
     EncoderConfig,
+    bert_config_from_dir,
+    check_supported,
+    clip_configs_from_dir,
     encoder_weights,
     param_specs,
     synth_state_dict,
@@ -222,7 +229,7 @@ def gemm_nt(A, W, bias, C, epilogue: int, kernel: str = "auto", lda: Optional[in
 # Tensors are passed by their data_ptr (a view's offset base included) and the shape arguments
 # are explicit, so a test can hand over strided, offset or aliased buffers. Launches go to the
 # current torch stream; nothing is allocated or synchronised here.
-ATTENTION_KERNELS = {"auto": 0, "flash16": 1, "seq64": 2}
+ATTENTION_KERNELS = {"auto": 0, "flash16": 1, "seq64": 2, "seqkv": 3}
 
 
 def _ptr(t):
@@ -256,10 +263,17 @@ def attention(qkv, out, B: int, L: int, H: int, head_dim: int, mask=None, causal
 
 
 def vit_im2col(img, out, B: int, S: int, P: int):
-    """K1 prologue: u8 ``img[B][S][S][3]`` -> fp16 ``out[B*(S/P)^2][3*P*P]`` (CLIP normalisation)."""
+    """K1 prologue: u8 ``img[B][S][S][3]`` -> fp16 ``out[B*(S/P)^2][Kpad]`` (CLIP normalisation);
+    ``Kpad = 3*P*P``, rounded up to a multiple of 64 with zero pad columns when ``P % 8 != 0``
+    (``vit_patch_kpad``)."""
     lib = _register_signatures()
     _native.check(lib.mrag_vit_im2col(_ptr(img), _ptr(out), B, S, P, _stream(img)), "mrag_vit_im2col")
     return out
+
+
+def vit_patch_kpad(P: int) -> int:
+    """Row length of the im2col output (and of the packed patch weight): P = 14 -> 640."""
+    return (3 * P * P + 63) // 64 * 64
 
 
 def vit_embed_ln(patch, cls, pos, gamma, beta, X, B: int, T: int, D: int, eps: float = 1e-5):
@@ -318,7 +332,7 @@ def load_encoder(cfg: EncoderConfig, model_name: Optional[str] = None, device: i
 
 
 def bench_clip_images(steps: int = 10, warmup: int = 2, batch: int = 256, device: int = 0,
-                      inflight: int = 3, streams=None) -> Dict:
+                      inflight: int = 3, streams=None, cfg: Optional[EncoderConfig] = None) -> Dict:
     """BASELINE config 2: CLIP ViT-B/32 image embeds/s on one GPU (batch 256 random
     224x224 u8 images resident in HBM, fp16 MFMA, synthetic weights).
 
@@ -331,12 +345,17 @@ def bench_clip_images(steps: int = 10, warmup: int = 2, batch: int = 256, device
     GEMM grids queue behind each other). inflight=1 runs one batch at a time (on its own stream,
     still without a host sync per batch). ``streams``: the HIP streams to run on (a serving
     process creates its request streams once at start-up; bench.py passes streams it made before
-    its other legs, so each lands on its own hardware queue, see bench.py _early_streams)."""
+    its other legs, so each lands on its own hardware queue, see bench.py _early_streams).
+    ``cfg``: another image tower (CLIP_VISION_B16, CLIP_VISION_L14; scripts/encoder_geometry_bench.py)."""
     import torch
+
+    cfg = CLIP_VISION_B32 if cfg is None else cfg
 
     inflight = max(1, int(inflight))
     dev = torch.device("cuda", device)
-    encs = [GpuEncoder(CLIP_VISION_B32, device=device) for _ in range(inflight)]
+    sd = None if cfg is CLIP_VISION_B32 else dict(synth_state_dict(cfg, 0))  # generated once for every handle
+    encs = [GpuEncoder(cfg, device=device, state_dict=sd) for _ in range(inflight)]
+    del sd
     if streams is None or len(streams) < inflight:
         streams = [torch.cuda.Stream(device=dev) for _ in range(inflight)]
     streams = list(streams)[:inflight]
@@ -357,7 +376,7 @@ def bench_clip_images(steps: int = 10, warmup: int = 2, batch: int = 256, device
     run(steps)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    flops_per_img = vit_flops_per_image(CLIP_VISION_B32)
+    flops_per_img = vit_flops_per_image(cfg)
     ips = batch * steps / dt
     return {
         "metric": "CLIP img-embeds/sec/GPU",
@@ -368,7 +387,10 @@ def bench_clip_images(steps: int = 10, warmup: int = 2, batch: int = 256, device
         "batches_in_flight": inflight,
         "ms_per_batch": round(dt / steps * 1e3, 3),
         "dtype": "fp16 MFMA (f32 accumulate, f32 residual stream)",
-        "workload": "BASELINE config 2: CLIP ViT-B/32 image tower, batch 256 random 224x224 u8 images, synthetic weights",
+        "workload": ("BASELINE config 2: CLIP ViT-B/32 image tower, batch 256 random 224x224 u8 images, synthetic weights"
+                     if cfg is CLIP_VISION_B32 else
+                     f"CLIP ViT image tower (hidden {cfg.hidden}, {cfg.layers} layers, patch {cfg.patch_size}), "
+                     f"batch {batch} random 224x224 u8 images, synthetic weights"),
         "roofline": {"bound": "mfma", "achieved": round(flops_per_img * ips / 1e12, 2), "peak": 2500.0,
                      "unit": "TFLOP/s", "frac": round(flops_per_img * ips / 1e12 / 2500.0, 4),
                      "algorithmic_flops_per_image": flops_per_img},
@@ -412,5 +434,6 @@ def smoke_encoders() -> None:
 
 __all__ = ["GpuEncoder", "load_encoder", "gemm_nt", "layernorm", "attention", "vit_im2col", "vit_embed_ln",
            "token_embed", "eos_rows", "mean_pool", "cls_head", "gather_rows", "bench_clip_images", "smoke_encoders", "CLIP_VISION_B32",
-           "CLIP_TEXT_B32", "MINILM_L6", "EncoderConfig", "param_specs", "vit_flops_per_image",
+           "CLIP_TEXT_B32", "CLIP_VISION_B16", "CLIP_VISION_L14", "CLIP_TEXT_L14", "MINILM_L6", "EncoderConfig",
+           "clip_configs_from_dir", "bert_config_from_dir", "check_supported", "vit_patch_kpad", "param_specs", "vit_flops_per_image",
            "text_flops_per_sequence"]

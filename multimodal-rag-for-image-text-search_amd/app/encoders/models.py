@@ -22,7 +22,8 @@ from app.encoders import CLIP_TEXT_B32, CLIP_VISION_B32, MINILM_L6, GpuEncoder, 
 from app.encoders.preprocess import (load_batch, load_batch_device, prepare_batch, resize_images, upload_decode,
                                       upload_resize)
 from app.encoders.tokenize import ClipTokenizer, WordPieceTokenizer
-from app.encoders.weights import encoder_weights, resolve_model_dir, synth_state_dict, synthetic_allowed, SYNTHETIC_ENV
+from app.encoders.weights import (SYNTHETIC_ENV, bert_config_from_dir, clip_configs_from_dir, encoder_weights,
+                                  has_config, resolve_model_dir, synth_state_dict, synthetic_allowed)
 
 
 def _device_index() -> int:
@@ -66,9 +67,12 @@ class MiniLMSentenceModel:
     def __init__(self, name: Optional[str] = None, device: Optional[int] = None):
         d = _model_dir(name, _WORDPIECE_FILES)
         self.device = _device_index() if device is None else device
-        self._pool = _HandlePool(_handle_maker(MINILM_L6, d, self.device))
+        # the checkpoint's own geometry (all-MiniLM-L12-v2: 12 layers); raises before the GPU is
+        # touched for one the encoder does not run. Without a config.json: all-MiniLM-L6-v2
+        self.cfg = bert_config_from_dir(d, 3) if has_config(d) else MINILM_L6
+        self._pool = _HandlePool(_handle_maker(self.cfg, d, self.device))
         self._pool.first()  # load now, as SentenceTransformer(name) does
-        self.tokenizer = WordPieceTokenizer(d, max_len=256)
+        self.tokenizer = WordPieceTokenizer(d, max_len=min(256, self.cfg.max_positions))
 
     @property
     def enc(self):
@@ -82,7 +86,7 @@ class MiniLMSentenceModel:
         import torch
 
         sentences = list(sentences)
-        out = torch.empty((len(sentences), MINILM_L6.hidden), dtype=torch.float32, device=f"cuda:{self.device}")
+        out = torch.empty((len(sentences), self.enc.out_dim), dtype=torch.float32, device=f"cuda:{self.device}")
         if not sentences:
             return out if convert_to_tensor else out.cpu().numpy()
         # length-sorted batches like sentence-transformers; rows are independent, so the
@@ -197,21 +201,20 @@ class ClipModel:
     def __init__(self, name: Optional[str] = None, device: Optional[int] = None):
         self.dir = _model_dir(name)  # raises here, as CLIPModel.from_pretrained would
         self.device = _device_index() if device is None else device
-        self._vision_pool = _HandlePool(_handle_maker(CLIP_VISION_B32, self.dir, self.device))
+        # the checkpoint's own geometry (ViT-B/32, B/16, L/14 at 224 pixels); raises before the GPU
+        # is touched for one the towers do not run. Without a config.json: ViT-B/32
+        if has_config(self.dir):
+            self.vision_cfg, self.text_cfg = clip_configs_from_dir(self.dir)
+        else:
+            self.vision_cfg, self.text_cfg = CLIP_VISION_B32, CLIP_TEXT_B32
+        self._vision_pool = _HandlePool(_handle_maker(self.vision_cfg, self.dir, self.device))
         self._text_pool = None
 
     def to(self, device):
         return self
 
     def _text_cfg(self):
-        cfg = CLIP_TEXT_B32
-        if self.dir and os.path.exists(os.path.join(self.dir, "config.json")):
-            tc = json.load(open(os.path.join(self.dir, "config.json"))).get("text_config", {})
-            eos = tc.get("eos_token_id", cfg.eos_token_id)
-            from dataclasses import replace
-
-            cfg = replace(cfg, eos_token_id=-1 if eos == 2 else int(eos))  # legacy configs pool at argmax(ids)
-        return cfg
+        return self.text_cfg
 
     @property
     def vision(self):
@@ -314,7 +317,7 @@ class CrossEncoderModel:
 
         d = _model_dir(model_name_or_path, _WORDPIECE_FILES, synthetic)
         self.device = _device_index() if device is None else device
-        self.cfg = MSMARCO_MINILM_L6_CE
+        self.cfg = bert_config_from_dir(d, 4) if has_config(d) else MSMARCO_MINILM_L6_CE
         self.enc = load_encoder(self.cfg, d, device=self.device, seed=seed, synthetic=d is None)
         self.tokenizer = WordPieceTokenizer(d, max_len=max_length or self.cfg.max_positions)
         self.num_labels = self.cfg.proj_dim

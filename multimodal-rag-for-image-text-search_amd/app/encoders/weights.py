@@ -59,6 +59,154 @@ MSMARCO_MINILM_L6_CE = EncoderConfig(kind=4, hidden=384, layers=6, heads=12, int
                                      vocab=30522, proj_dim=1, act=1, ln_eps=1e-12)
 
 
+# openai/clip-vit-base-patch16: the B/32 towers with 16-pixel patches (197 tokens)
+CLIP_VISION_B16 = EncoderConfig(kind=1, hidden=768, layers=12, heads=12, intermediate=3072, proj_dim=512,
+                                image_size=224, patch_size=16, act=0, ln_eps=1e-5)
+# openai/clip-vit-large-patch14: ViT-L/14 (257 tokens) and its wider text tower, projected to 768
+CLIP_VISION_L14 = EncoderConfig(kind=1, hidden=1024, layers=24, heads=16, intermediate=4096, proj_dim=768,
+                                image_size=224, patch_size=14, act=0, ln_eps=1e-5)
+CLIP_TEXT_L14 = EncoderConfig(kind=2, hidden=768, layers=12, heads=12, intermediate=3072, max_positions=77,
+                              vocab=49408, proj_dim=768, act=0, eos_token_id=49407, ln_eps=1e-5)
+
+_KIND_NAMES = {1: "CLIP vision tower", 2: "CLIP text tower", 3: "BERT sentence encoder", 4: "BERT cross-encoder"}
+_ACTS = {"quick_gelu": 0, "gelu": 1}
+IMAGE_SIZE = 224          # the preprocessing path (resize, centre crop) is 224-only
+MAX_ATTENTION_TOKENS = 512  # K4's longest sequence
+
+
+def check_supported(cfg: EncoderConfig, model: Optional[str] = None) -> EncoderConfig:
+    """Raise ValueError, before the GPU is touched, for a geometry the native encoders do not
+    run, naming the model and the limit broken: the limits of ``mrag_encoder_create`` plus the
+    224-pixel preprocessing path and K4's 512 tokens. Returns cfg."""
+    who = f"{_KIND_NAMES.get(cfg.kind, f'encoder kind {cfg.kind}')}" + (f" of {model}" if model else "")
+
+    def no(limit: str):
+        raise ValueError(f"{who} is not supported: {limit}")
+
+    if cfg.kind not in _KIND_NAMES:
+        no("kind must be 1 (CLIP vision), 2 (CLIP text), 3 (BERT) or 4 (BERT cross-encoder)")
+    if cfg.hidden <= 0 or cfg.hidden % 128 or cfg.hidden > 1024:
+        no(f"hidden size {cfg.hidden} must be a multiple of 128 and at most 1024")
+    if cfg.intermediate <= 0 or cfg.intermediate % 128:
+        no(f"intermediate size {cfg.intermediate} must be a multiple of 128")
+    if cfg.heads <= 0 or cfg.hidden % cfg.heads or cfg.hidden // cfg.heads not in (32, 64):
+        no(f"head size hidden / heads = {cfg.hidden} / {cfg.heads} must be 32 or 64")
+    if not 1 <= cfg.layers <= 64:
+        no(f"{cfg.layers} layers, must be 1 to 64")
+    if cfg.act not in (0, 1):
+        no(f"activation {cfg.act} must be 0 (quick_gelu) or 1 (gelu)")
+    if cfg.kind in (1, 2) and (cfg.proj_dim <= 0 or cfg.proj_dim % 128):
+        no(f"projection_dim {cfg.proj_dim} must be a multiple of 128")
+    if cfg.kind == 4 and not 1 <= cfg.proj_dim <= 64:
+        no(f"num_labels {cfg.proj_dim} must be 1 to 64")
+    if cfg.kind == 1:
+        if cfg.image_size != IMAGE_SIZE:
+            no(f"image_size {cfg.image_size} must be {IMAGE_SIZE} (the preprocessing path is {IMAGE_SIZE}-only)")
+        if cfg.patch_size < 1 or cfg.image_size % cfg.patch_size:
+            no(f"patch_size {cfg.patch_size} must divide image_size {cfg.image_size}")
+        tokens = (cfg.image_size // cfg.patch_size) ** 2 + 1
+        if tokens > MAX_ATTENTION_TOKENS:
+            no(f"(image_size / patch_size)^2 + 1 = {tokens} tokens, above attention's {MAX_ATTENTION_TOKENS}")
+    else:
+        if cfg.max_positions < 1:
+            no(f"max_position_embeddings {cfg.max_positions} must be at least 1")
+        if cfg.vocab < 1:
+            no(f"vocab_size {cfg.vocab} must be at least 1")
+    return cfg
+
+
+def _read_json(path: str) -> dict:
+    import json
+
+    with open(path) as f:
+        return json.load(f)
+
+
+def _act(name, who: str) -> int:
+    if name not in _ACTS:
+        raise ValueError(f"{who} is not supported: hidden_act {name!r} must be one of {sorted(_ACTS)}")
+    return _ACTS[name]
+
+
+def clip_configs_from_dir(path: str) -> Tuple[EncoderConfig, EncoderConfig]:
+    """(vision, text) EncoderConfig of a CLIP checkpoint directory from its ``config.json``
+    (``vision_config``, ``text_config``, top-level ``projection_dim``); a missing key takes
+    transformers' own default (CLIPVisionConfig / CLIPTextConfig: the B/32 geometry). A legacy
+    ``eos_token_id`` of 2 pools at argmax(ids) (-1), as transformers does. Both are checked
+    (check_supported), so an unsupported checkpoint raises ValueError here."""
+    c = _read_json(os.path.join(path, "config.json"))
+    mt = c.get("model_type", "clip")
+    if mt != "clip":
+        raise ValueError(f"CLIP model {path} is not supported: model_type {mt!r} must be 'clip'")
+    v, t = c.get("vision_config") or {}, c.get("text_config") or {}
+    proj = int(c.get("projection_dim", 512))
+    vision = EncoderConfig(
+        kind=1, hidden=int(v.get("hidden_size", 768)), layers=int(v.get("num_hidden_layers", 12)),
+        heads=int(v.get("num_attention_heads", 12)), intermediate=int(v.get("intermediate_size", 3072)),
+        proj_dim=proj, image_size=int(v.get("image_size", 224)), patch_size=int(v.get("patch_size", 32)),
+        act=_act(v.get("hidden_act", "quick_gelu"), f"CLIP vision tower of {path}"),
+        ln_eps=float(v.get("layer_norm_eps", 1e-5)))
+    eos = int(t.get("eos_token_id", 49407))
+    text = EncoderConfig(
+        kind=2, hidden=int(t.get("hidden_size", 512)), layers=int(t.get("num_hidden_layers", 12)),
+        heads=int(t.get("num_attention_heads", 8)), intermediate=int(t.get("intermediate_size", 2048)),
+        max_positions=int(t.get("max_position_embeddings", 77)), vocab=int(t.get("vocab_size", 49408)),
+        proj_dim=proj, act=_act(t.get("hidden_act", "quick_gelu"), f"CLIP text tower of {path}"),
+        eos_token_id=-1 if eos == 2 else eos,  # legacy configs pool at argmax(ids)
+        ln_eps=float(t.get("layer_norm_eps", 1e-5)))
+    return check_supported(vision, path), check_supported(text, path)
+
+
+def bert_config_from_dir(path: str, kind: int) -> EncoderConfig:
+    """EncoderConfig of a BERT checkpoint directory (kind 3: a sentence-transformers model, mean
+    pooling; kind 4: a BertForSequenceClassification cross-encoder) from its ``config.json``.
+    Missing keys take BertConfig's defaults. Raises ValueError for another ``model_type``, an
+    activation other than gelu, relative position embeddings, and, for kind 3, a
+    sentence-transformers pipeline that is not Transformer -> mean Pooling (-> Normalize): CLS or
+    max pooling in ``1_Pooling/config.json``, a ``Dense`` module in ``modules.json``."""
+    if kind not in (3, 4):
+        raise ValueError(f"bert_config_from_dir: kind {kind} must be 3 (sentence encoder) or 4 (cross-encoder)")
+    who = f"{_KIND_NAMES[kind]} of {path}"
+    c = _read_json(os.path.join(path, "config.json"))
+    mt = c.get("model_type", "bert")
+    if mt != "bert":
+        raise ValueError(f"{who} is not supported: model_type {mt!r} must be 'bert'")
+    pe = c.get("position_embedding_type", "absolute")
+    if pe != "absolute":
+        raise ValueError(f"{who} is not supported: position_embedding_type {pe!r} must be 'absolute'")
+    if _act(c.get("hidden_act", "gelu"), who) != 1:
+        raise ValueError(f"{who} is not supported: hidden_act {c.get('hidden_act')!r} must be 'gelu'")
+    proj = 0
+    if kind == 4:
+        # config.json keeps id2label, from which transformers derives num_labels (default 2)
+        proj = int(c["num_labels"]) if "num_labels" in c else len(c["id2label"]) if c.get("id2label") else 2
+    else:
+        pool = os.path.join(path, "1_Pooling", "config.json")
+        if os.path.isfile(pool):
+            p = _read_json(pool)
+            on = sorted(k for k, val in p.items() if k.startswith("pooling_mode_") and val is True)
+            if on != ["pooling_mode_mean_tokens"]:
+                raise ValueError(f"{who} is not supported: 1_Pooling/config.json asks for {on or 'no pooling'}, "
+                                 f"only mean pooling (pooling_mode_mean_tokens) runs here")
+        mods = os.path.join(path, "modules.json")
+        if os.path.isfile(mods):
+            for m in _read_json(mods):
+                t = str(m.get("type", "")).rsplit(".", 1)[-1]
+                if t not in ("Transformer", "Pooling", "Normalize"):
+                    raise ValueError(f"{who} is not supported: modules.json has a {t} module, only "
+                                     f"Transformer -> Pooling -> Normalize runs here")
+    cfg = EncoderConfig(
+        kind=kind, hidden=int(c.get("hidden_size", 768)), layers=int(c.get("num_hidden_layers", 12)),
+        heads=int(c.get("num_attention_heads", 12)), intermediate=int(c.get("intermediate_size", 3072)),
+        max_positions=int(c.get("max_position_embeddings", 512)), vocab=int(c.get("vocab_size", 30522)),
+        proj_dim=proj, act=1, ln_eps=float(c.get("layer_norm_eps", 1e-12)))
+    return check_supported(cfg, path)
+
+
+def has_config(path: Optional[str]) -> bool:
+    return bool(path) and os.path.isfile(os.path.join(path, "config.json"))
+
+
 def param_specs(cfg: EncoderConfig) -> List[Tuple[str, Tuple[int, ...], str]]:
     """(state-dict name, shape, init kind) of every parameter the forward reads."""
     D, I = cfg.hidden, cfg.intermediate

@@ -288,7 +288,7 @@ int ensure_workspace(mrag_encoder* e, int B, int T) {
   if (int rc = buf_ensure(e->w->QKV, tokens * 3 * D * 2)) return rc;
   if (int rc = buf_ensure(e->w->ATT, tokens * D * 2)) return rc;
   int64_t f16n = tokens * I;
-  if (c.kind == MRAG_ENC_CLIP_VISION) f16n = std::max<int64_t>(f16n, tokens * 3 * c.patch_size * c.patch_size);
+  if (c.kind == MRAG_ENC_CLIP_VISION) f16n = std::max<int64_t>(f16n, tokens * vit_patch_kpad(c.patch_size));
   if (int rc = buf_ensure(e->w->F16, f16n * 2)) return rc;
   if (c.kind == MRAG_ENC_CLIP_VISION) {
     if (int rc = buf_ensure(e->w->PATCH, tokens * D * 4)) return rc;
@@ -465,7 +465,7 @@ int run_graph(mrag_encoder* e, uint64_t key, std::vector<const void*> sig, hipSt
 int image_forward(mrag_encoder* e, const uint8_t* img, int B, float* dst, int normalize, hipStream_t s) {
   const auto& c = e->cfg;
   const int S = c.image_size, P = c.patch_size, G = S / P, T = G * G + 1, D = c.hidden;
-  const int Kp = 3 * P * P;
+  const int Kp = vit_patch_kpad(P);  // im2col rows and the packed weight share the zero-padded K
   float* X = (float*)e->w->X.p;
   if (int rc = launch_vit_im2col(img, (_Float16*)e->w->F16.p, B, S, P, s)) return rc;
   if (int rc = gemm(e->w->F16.p, e->patch_w.p, nullptr, e->w->PATCH.p, B * (T - 1), D, Kp, D, EPI_F32, s)) return rc;
@@ -512,10 +512,13 @@ int mrag_encoder_create(const mrag_encoder_config* cfg, int32_t device, mrag_enc
   if (c.kind == MRAG_ENC_CLIP_VISION || c.kind == MRAG_ENC_CLIP_TEXT)
     MRAG_REQUIRE(c.proj_dim % 128 == 0 && c.proj_dim > 0, "proj_dim must be a multiple of 128");
   if (c.kind == MRAG_ENC_BERT_PAIR) MRAG_REQUIRE(c.proj_dim >= 1 && c.proj_dim <= 64, "num_labels %d", c.proj_dim);
-  if (c.kind == MRAG_ENC_CLIP_VISION)
-    MRAG_REQUIRE(c.patch_size > 0 && c.image_size % c.patch_size == 0 && (3 * c.patch_size * c.patch_size) % 64 == 0 &&
-                     c.patch_size % 8 == 0,
-                 "image/patch size unsupported");
+  if (c.kind == MRAG_ENC_CLIP_VISION) {
+    MRAG_REQUIRE(c.patch_size >= 1 && c.image_size >= c.patch_size && c.image_size % c.patch_size == 0,
+                 "image size %d must be a positive multiple of the patch size %d", c.image_size, c.patch_size);
+    const int64_t grid = c.image_size / c.patch_size;
+    MRAG_REQUIRE(grid * grid + 1 <= 512, "image %d / patch %d gives %lld tokens, above attention's 512", c.image_size,
+                 c.patch_size, (long long)(grid * grid + 1));
+  }
   int ndev = 0;
   MRAG_HIP(hipGetDeviceCount(&ndev));
   MRAG_REQUIRE(device >= 0 && device < ndev, "device %d out of range", device);
@@ -627,7 +630,15 @@ int mrag_encoder_set_param(mrag_encoder* e, const char* cname, const float* data
   } else if (ends("class_embedding")) {
     rc = upload(e->cls, data, numel, false, s);
   } else if (ends("patch_embedding.weight")) {
-    rc = upload(e->patch_w, data, numel, true, s);  // [D][3][P][P] == [D][K] row-major
+    // [D][3][P][P] == [D][K] row-major, packed as [D][vit_patch_kpad(P)] with zero pad columns
+    const int64_t K = 3 * (int64_t)c.patch_size * c.patch_size, Kpad = vit_patch_kpad(c.patch_size);
+    if (Kpad == K) {
+      rc = upload(e->patch_w, data, numel, true, s);
+    } else {
+      std::vector<float> padded((size_t)D * Kpad, 0.f);
+      for (int64_t d = 0; d < D; ++d) memcpy(&padded[(size_t)d * Kpad], data + d * K, (size_t)K * 4);
+      rc = upload(e->patch_w, padded.data(), D * Kpad, true, s);
+    }
   } else if (ends("position_embedding.weight") || ends("position_embeddings.weight")) {
     rc = upload(e->pos, data, numel, false, s);
   } else if (ends("token_embedding.weight") || ends("word_embeddings.weight")) {
@@ -1022,7 +1033,7 @@ int mrag_attention(const void* qkv, void* out, const int32_t* mask, int32_t B, i
 
 int mrag_vit_im2col(const uint8_t* img, void* out, int32_t B, int32_t S, int32_t P, void* stream) {
   MRAG_REQUIRE(img && out, "NULL pointer");
-  MRAG_REQUIRE(B >= 0 && P > 0 && P % 8 == 0 && S >= P && S % P == 0, "vit_im2col: B=%d S=%d P=%d unsupported", B, S, P);
+  MRAG_REQUIRE(B >= 0 && P >= 1 && S >= P && S % P == 0, "vit_im2col: B=%d S=%d P=%d unsupported", B, S, P);
   MRAG_REQUIRE(((uintptr_t)out & 15) == 0, "vit_im2col: out must be 16-byte aligned");
   return launch_vit_im2col(img, (_Float16*)out, B, S, P, (hipStream_t)stream);
 }

@@ -45,9 +45,13 @@ enum GemmKernel { GEMM_AUTO = 0, GEMM_K3 = 1, GEMM_K3D = 2, GEMM_K3S = 3, GEMM_K
 int launch_gemm(const GemmArgs& g, int epi, hipStream_t s, int kernel = GEMM_AUTO);
 bool gemm_ws_fits(const GemmArgs& g, int epi);
 int launch_layernorm(const LayerNormArgs& a, hipStream_t s);
-// kernel: ATTN_AUTO (seq64 for 33 <= L <= 64, flash16 otherwise) or one kernel forced (bit-identity tests)
-enum AttentionKernel { ATTN_AUTO = 0, ATTN_FLASH16 = 1, ATTN_SEQ64 = 2 };
+// kernel: ATTN_AUTO (seq64 for 33 <= L <= 64, seqkv for 65 <= L <= 320, flash16 otherwise) or one
+// kernel forced (bit-identity tests, timing)
+enum AttentionKernel { ATTN_AUTO = 0, ATTN_FLASH16 = 1, ATTN_SEQ64 = 2, ATTN_SEQKV = 3 };
 int launch_attention(const AttentionArgs& a, int dh, hipStream_t s, int kernel = ATTN_AUTO);
+// Row length (halves) of the im2col output and of the packed patch-embedding weight: 3 P P, rounded
+// up to the GEMM's K granule of 64 when P is no multiple of 8 (P = 14: 588 -> 640; zero pad columns).
+inline int vit_patch_kpad(int P) { return (3 * P * P + 63) / 64 * 64; }
 int launch_vit_im2col(const uint8_t* img, _Float16* out, int B, int S, int P, hipStream_t s);
 int launch_vit_embed_ln(const float* patch, const float* cls, const float* pos, const float* gamma, const float* beta,
                         float* X, int B, int T, int D, float eps, hipStream_t s);

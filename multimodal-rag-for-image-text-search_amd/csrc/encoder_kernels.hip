@@ -1442,6 +1442,136 @@ __global__ __launch_bounds__(256) void attention_seq64_kernel(AttentionArgs a) {
   }
 }
 
+// K4 v3, one (sequence, head) per workgroup for 65 <= L <= 320 (the 197 tokens of ViT-B/16, the 257
+// of ViT-L/14): attention_seq64_kernel with any number of 16-query blocks. The head's K and V rows
+// (16 * ceil(L / 16) of them, zeros past L) are staged ONCE into dynamic LDS by all 512 threads, K
+// under the seq64 swizzle and V under v_off, every global load of the stage (K, V, the mask words,
+// the wave's first Q fragments) issued before the first LDS store; flash16 fetches and stages them
+// once per 16-query block, 13 or 17 times per head at those lengths. The eight waves then walk the
+// query blocks, block qb on wave qb % 8, the next block's Q fragments loaded while the current one
+// is computed. K + V take 2 * 16 ceil(L / 16) * DH * 2 bytes: 52 KiB at L = 197 and DH = 64 (three
+// workgroups per CU), 80 KiB at L = 320 (two); the key flags are wave ballots in SGPRs (bit i of
+// word j: key 64 j + i is inside L and passes the mask), not LDS, so that two 80 KiB workgroups
+// still fit the CU's 160 KiB. The per-wave arithmetic is attention_flash16_kernel's, operand for
+// operand, with the same skip of fully masked key blocks and the same causal limit: the outputs are
+// bit-identical to it. NST = staging steps per thread = ceil(rows * DH / 8 / 512).
+constexpr int SKV_THREADS = 512, SKV_WAVES = SKV_THREADS / 64, SKV_MIN_L = 65, SKV_MAX_L = 320;
+template <int DH, int NST>
+__global__ __launch_bounds__(SKV_THREADS) void attention_seqkv_kernel(AttentionArgs a) {
+  constexpr int KS = DH / 32, DB = DH / 16, CH = DH / 8;
+  constexpr int NMW = SKV_MAX_L / 64;  // 64-key mask words
+  typedef _Float16 half4_v __attribute__((ext_vector_type(4)));
+  extern __shared__ __attribute__((aligned(16))) _Float16 skv_lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int L = a.L, nqb = (L + 15) >> 4, rows = 16 * nqb;
+  _Float16* Ks = skv_lds;
+  _Float16* Vs = skv_lds + rows * DH;
+  const int bh = blockIdx.x, hd = bh % a.H, b = bh / a.H;
+  const int D = a.H * DH;
+  const size_t rs = (size_t)3 * D;
+  const _Float16* base = a.qkv + (size_t)b * L * rs + hd * DH;
+  // (rows past L load row L - 1, unconditionally, and are zeroed at the store, as in seq64)
+  half8 kst[NST], vst[NST];
+#pragma unroll
+  for (int t = 0; t < NST; ++t) {
+    const int idx = threadIdx.x + SKV_THREADS * t, key = min(idx / CH, L - 1), ch = idx % CH;
+    kst[t] = *(const half8*)(base + (size_t)key * rs + D + 8 * ch);
+    vst[t] = *(const half8*)(base + (size_t)key * rs + 2 * D + 8 * ch);
+  }
+  auto load_q = [&](int qb, half8(&q)[KS]) {
+    const int qrow = min(16 * qb + c, L - 1);
+#pragma unroll
+    for (int st = 0; st < KS; ++st) q[st] = *(const half8*)(base + (size_t)qrow * rs + 32 * st + 8 * g);
+  };
+  half8 qnext[KS];
+  load_q(w, qnext);
+  int mv[NMW];
+#pragma unroll
+  for (int j = 0; j < NMW; ++j) mv[j] = a.mask ? a.mask[(size_t)b * L + min(lane + 64 * j, L - 1)] : 1;
+  auto k_off = [&](int r, int ch) { return r * DH + 8 * (ch ^ ((r >> 1) & (CH - 1))); };
+#pragma unroll
+  for (int t = 0; t < NST; ++t) {
+    const int idx = threadIdx.x + SKV_THREADS * t, key = idx / CH, ch = idx % CH;
+    if (key < rows) {
+      *(half8*)(Ks + k_off(key, ch)) = key < L ? kst[t] : half8{};
+      *(half8*)(Vs + v_off<DH>(key, 8 * ch)) = key < L ? vst[t] : half8{};
+    }
+  }
+  unsigned long long mw[NMW];
+#pragma unroll
+  for (int j = 0; j < NMW; ++j) mw[j] = __ballot(lane + 64 * j < L && mv[j] != 0);
+  __syncthreads();
+  for (int qb = w; qb < nqb; qb += SKV_WAVES) {  // whole waves (the transposed reads need EXEC all ones)
+    const int qrow = 16 * qb + c;
+    half8 qf[KS];
+#pragma unroll
+    for (int st = 0; st < KS; ++st) qf[st] = qrow < L ? qnext[st] : half8{};
+    load_q(qb + SKV_WAVES, qnext);  // clamped to row L - 1: past the last block it is never used
+    f32x4 o[DB];
+#pragma unroll
+    for (int db = 0; db < DB; ++db) o[db] = f32x4{};
+    float m = -INFINITY, l = 0.f;
+    const int nkb = a.causal ? min(nqb, qb + 1) : nqb;
+    for (int kb = 0; kb < nkb; ++kb) {
+      const unsigned long long word = kb < 4 ? mw[0] : kb < 8 ? mw[1] : kb < 12 ? mw[2] : kb < 16 ? mw[3] : mw[4];
+      const unsigned bits = (unsigned)(word >> (16 * (kb & 3))) & 0xffffu;  // the block's 16 key flags
+      bool kv[4], any_ok = false;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = 16 * kb + 4 * g + r;
+        kv[r] = ((bits >> (4 * g + r)) & 1u) != 0 && (!a.causal || key <= qrow);
+        any_ok |= kv[r];
+      }
+      if (!__any(any_ok)) continue;  // wave-uniform: a fully masked key block
+      f32x4 sacc = {};
+#pragma unroll
+      for (int st = 0; st < KS; ++st) {
+        const half8 kf = *(const half8*)(Ks + k_off(16 * kb + c, 4 * st + g));
+        sacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[st], sacc, 0, 0, 0);
+      }
+      float sv[4], bmax = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        sv[r] = kv[r] ? sacc[r] * a.scale : -INFINITY;
+        bmax = fmaxf(bmax, sv[r]);
+      }
+      bmax = fmaxf(bmax, __shfl_xor(bmax, 16));
+      bmax = fmaxf(bmax, __shfl_xor(bmax, 32));
+      const float mn = fmaxf(m, bmax);
+      const float alpha = m == -INFINITY ? 0.f : __expf(m - mn);
+      half4_v pf;
+      float ps = 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pv = sv[r] == -INFINITY ? 0.f : __expf(sv[r] - mn);
+        pf[r] = (_Float16)pv;
+        ps += pv;
+      }
+      ps += __shfl_xor(ps, 16);
+      ps += __shfl_xor(ps, 32);
+      l = l * alpha + ps;
+      m = mn;
+#pragma unroll
+      for (int db = 0; db < DB; ++db) {
+        o[db] *= alpha;
+        const half4_t vt = lds_read_tr16(Vs + v_off<DH>(16 * kb + 4 * g + (c >> 2), 16 * db + 4 * (c & 3)));
+        o[db] = __builtin_amdgcn_mfma_f32_16x16x16f16(vt, pf, o[db], 0, 0, 0);
+      }
+    }
+    if (qrow < L) {
+      const float inv = l > 0.f ? 1.f / l : 0.f;
+      _Float16* orow = a.out + ((size_t)b * L + qrow) * D + hd * DH + 4 * g;
+#pragma unroll
+      for (int db = 0; db < DB; ++db) {
+        const half4_t h = {(_Float16)(o[db][0] * inv), (_Float16)(o[db][1] * inv), (_Float16)(o[db][2] * inv),
+                           (_Float16)(o[db][3] * inv)};
+        *(half4_t*)(orow + 16 * db) = h;
+      }
+    }
+  }
+}
+
 __global__ void vit_im2col_kernel(const uint8_t* __restrict__ img, _Float16* __restrict__ out, int B, int S,
                                   int P) {
   const int G = S / P;
@@ -1464,6 +1594,42 @@ __global__ void vit_im2col_kernel(const uint8_t* __restrict__ img, _Float16* __r
     v8[t] = (_Float16)((x - mean) / stdv);
   }
   *(half8*)(out + row * K + k8) = *(half8*)v8;
+}
+
+// K1 for a patch size that is no multiple of 8 (ViT-L/14: 3 * 14 * 14 = 588 columns), same
+// arithmetic and (c, kh, kw) order: the output rows are vit_patch_kpad(P) halves long (588 -> 640,
+// the GEMM's K granule), one thread per 8 columns of a row, each column's pixel addressed on its own
+// (a group of 8 crosses kernel rows and channels). The columns from 3 P P up are written as +0 by the
+// same 16-byte stores on every launch: the buffer is a workspace that later layers reuse as a GEMM
+// operand, and a stale pad value (an Inf, a NaN) times the weight's zero pad would not be zero.
+__global__ __launch_bounds__(256) void vit_im2col_pad_kernel(const uint8_t* __restrict__ img,
+                                                             _Float16* __restrict__ out, int B, int S, int P,
+                                                             int Kpad) {
+  const int G = S / P;
+  const int K = 3 * P * P;
+  const int64_t total8 = (int64_t)B * G * G * (Kpad / 8);
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total8) return;
+  const int64_t row = idx / (Kpad / 8);
+  const int k8 = (int)(idx - row * (Kpad / 8)) * 8;
+  const int b = (int)(row / (G * G)), pidx = (int)(row % (G * G));
+  const int py = pidx / G, px = pidx % G;
+  const uint8_t* patch = img + (((size_t)b * S + (size_t)py * P) * S + (size_t)px * P) * 3;
+  half8 v8;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const int k = k8 + t;
+    _Float16 v = (_Float16)0.f;
+    if (k < K) {
+      const int c = k / (P * P), kh = (k / P) % P, kw = k % P;
+      const float mean = c == 0 ? 0.48145466f : (c == 1 ? 0.4578275f : 0.40821073f);
+      const float stdv = c == 0 ? 0.26862954f : (c == 1 ? 0.26130258f : 0.27577711f);
+      const float x = (float)((double)patch[((size_t)kh * S + kw) * 3 + c] * (1.0 / 255.0));
+      v = (_Float16)((x - mean) / stdv);
+    }
+    v8[t] = v;
+  }
+  *(half8*)(out + row * Kpad + k8) = v8;
 }
 
 // K1 for P = 32 (ViT-B/32), same arithmetic: one thread per (patch, kernel row kh). The 32
@@ -1758,15 +1924,62 @@ int launch_vit_embed_ln(const float* patch, const float* cls, const float* pos, 
   return MRAG_OK;
 }
 
+// attention_seqkv_kernel<DH, NST> on B * H workgroups with K + V in dynamic LDS (above 64 KiB
+// from L = 257 at DH = 64: the function's limit is raised first)
+template <int DH, int NST>
+int launch_seqkv(const AttentionArgs& a, hipStream_t s) {
+  const int rows = (a.L + 15) / 16 * 16;
+  const size_t lds = (size_t)2 * rows * DH * 2;
+  if (lds > 65536)
+    MRAG_HIP(hipFuncSetAttribute((const void*)attention_seqkv_kernel<DH, NST>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((attention_seqkv_kernel<DH, NST>), dim3((unsigned)((int64_t)a.B * a.H)), dim3(SKV_THREADS), lds, s,
+                     a);
+  MRAG_CHECK_LAUNCH();
+  return MRAG_OK;
+}
+
+int launch_attention_seqkv(const AttentionArgs& a, int dh, hipStream_t s) {
+  MRAG_REQUIRE((int64_t)a.B * a.H < (1ll << 31), "attention: batch too large");
+  const int rows = (a.L + 15) / 16 * 16;
+  const int nst = (rows * (dh / 8) + SKV_THREADS - 1) / SKV_THREADS;  // 2..5 at dh = 64, 1..3 at dh = 32
+  if (dh == 64) {
+    switch (nst) {
+      case 2: return launch_seqkv<64, 2>(a, s);
+      case 3: return launch_seqkv<64, 3>(a, s);
+      case 4: return launch_seqkv<64, 4>(a, s);
+      case 5: return launch_seqkv<64, 5>(a, s);
+    }
+  } else {
+    switch (nst) {
+      case 1: return launch_seqkv<32, 1>(a, s);
+      case 2: return launch_seqkv<32, 2>(a, s);
+      case 3: return launch_seqkv<32, 3>(a, s);
+    }
+  }
+  return mrag::fail(MRAG_ERR_ARG, "attention seqkv: L=%d head_dim=%d has no staging variant", a.L, dh);
+}
+
+// The automatic rule takes seqkv over its whole range, whatever the mask and the causal flag.
+// Attention alone, flash16 / seqkv interleaved over seven pairs of 50 launches on one box
+// (profiles/attention_seqkv_ab.jsonl), us per launch: ViT-B/16 (B 256, L 197) 176-214 against
+// 134-147, ViT-L/14 (B 128, L 257) 185-190 against 145-148, CLIP text (B 1000, L 77, causal, ragged
+// mask) 105-110 against 94-95, MiniLM (B 256, L 256, dh 32) 206-207 against 106 with a ragged mask
+// and 160-164 against 127-132 without: seqkv ahead in every pair by more than either kernel's spread.
+bool seqkv_auto(const AttentionArgs& a) { return a.L >= SKV_MIN_L && a.L <= SKV_MAX_L; }
+
 int launch_attention(const AttentionArgs& a, int dh, hipStream_t s, int kernel) {
   if (a.B <= 0) return MRAG_OK;
   MRAG_REQUIRE(a.L >= 1 && a.L <= 512, "attention: L=%d unsupported (1..512)", a.L);
   MRAG_REQUIRE(dh == 64 || dh == 32, "attention: head_dim %d unsupported (32, 64)", dh);
   const int64_t items = (int64_t)a.B * a.H * ((a.L + 15) / 16);
   MRAG_REQUIRE(items < (1ll << 33), "attention: batch too large");
-  MRAG_REQUIRE(kernel >= ATTN_AUTO && kernel <= ATTN_SEQ64, "attention: bad kernel %d", kernel);
+  MRAG_REQUIRE(kernel >= ATTN_AUTO && kernel <= ATTN_SEQKV, "attention: bad kernel %d", kernel);
   MRAG_REQUIRE(kernel != ATTN_SEQ64 || (a.L > 32 && a.L <= 64), "attention: the seq64 kernel needs 33 <= L <= 64 (L=%d)",
                a.L);
+  MRAG_REQUIRE(kernel != ATTN_SEQKV || (a.L >= SKV_MIN_L && a.L <= SKV_MAX_L),
+               "attention: the seqkv kernel needs %d <= L <= %d (L=%d)", SKV_MIN_L, SKV_MAX_L, a.L);
+  if (kernel == ATTN_SEQKV || (kernel == ATTN_AUTO && seqkv_auto(a))) return launch_attention_seqkv(a, dh, s);
   // one workgroup per (sequence, head): the ViT's 50 tokens
   if (kernel == ATTN_SEQ64 || (kernel == ATTN_AUTO && a.L > 32 && a.L <= 64)) {
     hipLaunchKernelGGL(dh == 64 ? attention_seq64_kernel<64> : attention_seq64_kernel<32>,
@@ -1780,6 +1993,16 @@ int launch_attention(const AttentionArgs& a, int dh, hipStream_t s, int kernel) 
 }
 
 int launch_vit_im2col(const uint8_t* img, _Float16* out, int B, int S, int P, hipStream_t s) {
+  if (P % 8 != 0) {  // rows padded to vit_patch_kpad(P) halves
+    const int Kpad = vit_patch_kpad(P);
+    const int64_t n = (int64_t)B * (S / P) * (S / P) * (Kpad / 8);
+    if (n == 0) return MRAG_OK;
+    MRAG_REQUIRE((n + 255) / 256 < (1ll << 31), "vit_im2col: batch too large");
+    hipLaunchKernelGGL(vit_im2col_pad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, out, B, S, P,
+                       Kpad);
+    MRAG_CHECK_LAUNCH();
+    return MRAG_OK;
+  }
   const int64_t total8 = (int64_t)B * (S / P) * (S / P) * (3 * P * P / 8);
   if (total8 == 0) return MRAG_OK;
   if (P == 32 && S % 16 == 0 && ((uintptr_t)img & 15) == 0) {
