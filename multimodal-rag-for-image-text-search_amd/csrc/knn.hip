@@ -18,7 +18,9 @@
 //            approx >= exact_k - EPS is collected — a superset of the true top-k
 //   K10    : exact f64 rescoring of the collected rows + ordered selection
 // The result is therefore exact for any data (ties and duplicates included), and
-// the common case costs one fp16 MFMA pass plus a small gather.
+// the common case costs one fp16 MFMA pass plus a small gather. Which scan a search takes, its
+// grid, the sample pass and K8's sizes are decided in knn_plan.h (plain C++, tested on the CPU);
+// the host code at the end of this file runs that plan in stages.
 //
 // HBM layout per index (rows padded to DP = dim rounded up to 128):
 //   x16    [cap][DP] fp16   normalised scan copy   (streamed by K7, 1 KiB rows at 512-d)
@@ -35,24 +37,20 @@
 
 #include "common.h"
 #include "knn_generic.h"
+#include "knn_plan.h"
 
 #define AS1 __attribute__((address_space(1)))
 #define AS3 __attribute__((address_space(3)))
 
+// the tile / group / list constants the kernels share with the search plan, and the plan itself
+using namespace mrag_knn;
+
 namespace {
 
-constexpr int TILE_ROWS = 64;
 constexpr int SCAN_WAVES = 8;
 constexpr int SCAN_THREADS = SCAN_WAVES * 64;
-constexpr int QPW = 32;                     // queries per wave (MFMA 32x32 N dim)
-constexpr int QPG = SCAN_WAVES * QPW;       // queries per workgroup
-constexpr int MAX_MERGE_ENTRIES = 4096;     // splits * KL cap (LDS sort in K8)
-constexpr int MAX_K = 256;
+static_assert(SCAN_WAVES * QPW == QPG, "v1: one 32-query block per wave");
 constexpr int MERGE_THREADS = 256;
-#ifndef MRAG_SAMPLE_STRIDE
-#define MRAG_SAMPLE_STRIDE 16
-#endif
-constexpr int SAMPLE_STRIDE = MRAG_SAMPLE_STRIDE;  // K7 sample pre-pass: every 16th tile of a split (A/B builds: -D)
 
 // |approx - exact| bound for the fp16 scan:
 //   fp16 rounding of both unit vectors: (2u + u^2) * sum|q_i x_i| <= 9.77e-4 (u = 2^-11)
@@ -1027,8 +1025,7 @@ struct ResolveParams {
   int32_t* part_i;
   float* part_tau;
 };
-constexpr int XLISTS = 4, XCAP = XLISTS * 8;
-constexpr int REC_ID_BITS_MAX = 10;  // id field of a packed record entry (qrec packs beside it)
+constexpr int XCAP = XLISTS * 8;
 
 __global__ __launch_bounds__(64) void sample_resolve_kernel(ResolveParams p) {
   using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
@@ -1737,9 +1734,26 @@ __global__ void fill_empty_kernel(float* s, double* s64, int64_t* r, int64_t n) 
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
+// A device allocation owned by its holder: move-only, freed when the holder is destroyed (which
+// must happen with the allocation's device current: see mrag_knn_destroy).
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      if (p) (void)hipFree(p);
+      p = std::exchange(o.p, nullptr);
+      bytes = std::exchange(o.bytes, 0);
+    }
+    return *this;
+  }
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
 };
 
 int ensure(DevBuf& b, size_t bytes) {
@@ -1755,19 +1769,13 @@ int ensure(DevBuf& b, size_t bytes) {
   return MRAG_OK;
 }
 
-void release(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-}
-
+// Kernel instances for a plan's fields (knn_plan.h decides; these only look up).
 typedef void (*scan_fn)(ScanParams);
 
 template <int DP>
 scan_fn pick_scan(int KL, bool collect) {
   if (collect) return knn_scan_kernel<DP, 8, true>;
-  // Deeper lists keep 2*KL more VGPRs live next to the DP/4 query-fragment registers;
-  // kl_for() caps KL where it would spill (the certificate stays exact either way).
+  // kl_for() caps KL per width, so only these depths are instantiated
   if constexpr (DP >= 512) {
     return knn_scan_kernel<DP, 8, false>;
   } else if constexpr (DP >= 256) {
@@ -1776,13 +1784,6 @@ scan_fn pick_scan(int KL, bool collect) {
     return KL <= 8 ? knn_scan_kernel<DP, 8, false>
                    : (KL <= 16 ? knn_scan_kernel<DP, 16, false> : knn_scan_kernel<DP, 32, false>);
   }
-}
-
-// Per-lane list depth: >= k where registers allow (DP/4 VGPRs hold the query fragments).
-int kl_for(int k, int DP) {
-  if (k <= 8 || DP >= 512) return 8;
-  if (k <= 16 || DP >= 256) return 16;
-  return 32;
 }
 
 template <int MODE, int QB>
@@ -1802,19 +1803,6 @@ scan_fn get_scan3(int DP, int mode, int qb) {
   return mode == 2 ? get_scan3m<2, 4>(DP) : mode == 1 ? get_scan3m<1, 4>(DP) : get_scan3m<0, 4>(DP);
 }
 
-// Query blocks per wave of the v3 scan for a batch: 1 (K7s, 64 queries per workgroup) while the
-// batch fits one small group, else 4 (256 per workgroup).
-int scan3_qb(int64_t nq) { return nq <= 64 ? 1 : 4; }
-
-// Sample pre-pass stride for k: the main scan's fires grow with the rows above the seed, about
-// k x stride, so k > 16 samples every 4th tile (512k x 512, k = 50: search 0.824 -> 0.736 ms,
-// scan 0.659 -> 0.501; stride 8: 0.748; notes/knn_scan_experiments.md).
-int sample_stride_for(int k) { return k > 16 ? 4 : SAMPLE_STRIDE; }
-// k <= 16: the counting sample pass (MODE 2 + sample_resolve_kernel) takes its tiles for good and
-// the main scan skips them; k > 16 keeps the seed-only pass over every 4th tile and a main scan
-// over all tiles (the rows above its seed, about k x stride, would not fit the extra lists).
-bool counting_sample_for(int k) { return k <= 16; }
-
 scan_fn get_scan(int DP, int KL, bool collect) {
   switch (DP) {
     case 128: return pick_scan<128>(KL, collect);
@@ -1823,12 +1811,6 @@ scan_fn get_scan(int DP, int KL, bool collect) {
     case 512: return pick_scan<512>(KL, collect);
     default: return nullptr;
   }
-}
-
-int64_t next_pow2(int64_t x) {
-  int64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
 }
 
 }  // namespace
@@ -1847,6 +1829,14 @@ struct SearchCtx {
   hipEvent_t null_ev = nullptr;      // device inputs on the NULL stream: the search waits for it
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // scan timing (mrag_knn_profile)
   mrag_knn::Workspace gws[8];               // K7g buffers
+  // on the index's device (ctx_get, ~mrag_knn_index); the DevBufs free themselves
+  ~SearchCtx() {
+    mrag_knn::release(gws);
+    if (host_counters) (void)hipHostFree(host_counters);
+    if (host_fail) (void)hipHostFree(host_fail);
+    for (hipEvent_t e : {done, null_ev, ev0, ev1})
+      if (e) (void)hipEventDestroy(e);
+  }
 };
 
 struct mrag_knn_index {
@@ -1869,6 +1859,11 @@ struct mrag_knn_index {
   bool profile = false;
   double scan_ms = 0.0;
   int64_t scan_launches = 0;
+  // with `device` current and nothing in flight (mrag_knn_destroy); the DevBufs free themselves
+  ~mrag_knn_index() {
+    for (SearchCtx* c : ctx_all) delete c;
+    if (stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 namespace {
@@ -1885,21 +1880,6 @@ int wait_stream(SearchCtx* c, hipStream_t s) {
   }
   if (e != hipSuccess) return mrag::fail(MRAG_ERR_HIP, "search: %s", hipGetErrorString(e));
   return MRAG_OK;
-}
-
-void ctx_free_all(SearchCtx* c) {
-  for (DevBuf* b : {&c->qin, &c->q32, &c->qn, &c->q16, &c->part_s, &c->part_i, &c->thresh, &c->fail_list,
-                    &c->counters, &c->cand_cnt, &c->cand, &c->scratch, &c->out_s, &c->out_s64, &c->out_r,
-                    &c->theta, &c->part_tau, &c->rec})
-    release(*b);
-  mrag_knn::release(c->gws);
-  if (c->host_counters) (void)hipHostFree(c->host_counters);
-  if (c->host_fail) (void)hipHostFree(c->host_fail);
-  if (c->done) (void)hipEventDestroy(c->done);
-  if (c->null_ev) (void)hipEventDestroy(c->null_ev);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  delete c;
 }
 
 // A free search context of ix (created on first need); returned by ctx_put.
@@ -1920,7 +1900,7 @@ int ctx_get(mrag_knn_index* ix, SearchCtx** out) {
   if (e == hipSuccess) e = hipEventCreate(&c->ev0);
   if (e == hipSuccess) e = hipEventCreate(&c->ev1);
   if (e != hipSuccess) {
-    ctx_free_all(c);
+    delete c;
     return mrag::fail(MRAG_ERR_HIP, "search context: %s", hipGetErrorString(e));
   }
   std::lock_guard<std::mutex> lk(ix->pool_mu);
@@ -1942,7 +1922,7 @@ int grow(mrag_knn_index* ix, int64_t need) {
   if (need <= ix->cap) return MRAG_OK;
   int64_t ncap = std::max<int64_t>({(int64_t)TILE_ROWS, ix->cap * 2, need});
   ncap = (ncap + 767) / 768 * 768;  // a multiple of the 64- and 48-row scan tiles and of K7g's 128-column GEMM tile
-  DevBuf nx16, nx32, nxn, nlab;
+  DevBuf nx16, nx32, nxn, nlab;  // an error return frees what was allocated so far
   if (int rc = ensure(nx16, (size_t)ncap * ix->DP * 2)) return rc;
   if (int rc = ensure(nx32, (size_t)ncap * ix->DP * 4)) return rc;
   if (int rc = ensure(nxn, (size_t)ncap * 8)) return rc;
@@ -1961,15 +1941,314 @@ int grow(mrag_knn_index* ix, int64_t need) {
     MRAG_HIP(hipMemcpyAsync(nlab.p, ix->labels.p, (size_t)ix->n * 4, hipMemcpyDeviceToDevice, s));
   }
   MRAG_HIP(hipStreamSynchronize(s));
-  release(ix->x16);
-  release(ix->x32);
-  release(ix->xn);
-  release(ix->labels);
-  ix->x16 = nx16;
-  ix->x32 = nx32;
-  ix->xn = nxn;
-  ix->labels = nlab;
+  ix->x16 = std::move(nx16);  // frees the old buffers
+  ix->x32 = std::move(nx32);
+  ix->xn = std::move(nxn);
+  ix->labels = std::move(nlab);
   ix->cap = ncap;
+  return MRAG_OK;
+}
+
+// ---- one search, in stages (mrag_knn_search) ----
+
+// What every stage of a search reads: the call's arguments, the leased context, the stream and
+// the device-side output destinations.
+struct Search {
+  mrag_knn_index* ix;
+  SearchCtx* c;
+  hipStream_t s;
+  const float* queries;
+  bool host;  // queries and outputs are host pointers
+  int64_t nq;
+  int k, label_filter;
+  int64_t row_offset;
+  float* os;
+  double* os64;  // may be null
+  int64_t* orr;
+  bool profile;
+};
+
+// What a search reports (mrag_knn_last_stats, mrag_debug_knn_last_collect).
+struct SearchStats {
+  int64_t uncertified = 0, retries = 0;
+  int32_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // see mrag_knn_index::last_info
+};
+
+// The context buffers of a fused search, sized from its plan (the query buffers: stage_queries;
+// the collect buffers: collect_stage).
+int size_buffers(SearchCtx* c, const SearchPlan& p) {
+  const size_t Qp = (size_t)p.Qp, lists = (size_t)(p.S + p.SX);
+  if (int rc = ensure(c->part_s, lists * Qp * p.KL * 4)) return rc;
+  if (int rc = ensure(c->part_i, lists * Qp * p.KL * 4)) return rc;
+  if (int rc = ensure(c->thresh, Qp * 4)) return rc;
+  if (int rc = ensure(c->fail_list, Qp * 4)) return rc;
+  if (int rc = ensure(c->counters, 16)) return rc;
+  if (int rc = ensure(c->cand_cnt, Qp * 4)) return rc;
+  if (int rc = ensure(c->theta, Qp * 4)) return rc;
+  if (p.path == SearchPath::V3)
+    if (int rc = ensure(c->part_tau, lists * Qp * 4)) return rc;
+  if (p.counting)
+    if (int rc = ensure(c->rec, (size_t)p.S * Qp * 16 * 4)) return rc;
+  return MRAG_OK;
+}
+
+// Query staging: f32 queries (copied in when on the host) -> q32 / qn / q16 of the plan's query
+// slots. A fused search sizes the rest of its context here, between the query buffers and the
+// prep launch, which clears the per-search words there (counters, collect counts, thresholds).
+int stage_queries(const Search& q, const SearchPlan& p) {
+  SearchCtx* c = q.c;
+  const int D = q.ix->D, DP = q.ix->DP;
+  const float* qsrc = q.queries;
+  if (q.host) {
+    if (int rc = ensure(c->qin, (size_t)q.nq * D * 4)) return rc;
+    MRAG_HIP(hipMemcpyAsync(c->qin.p, q.queries, (size_t)q.nq * D * 4, hipMemcpyHostToDevice, q.s));
+    qsrc = (const float*)c->qin.p;
+  }
+  if (int rc = ensure(c->q32, (size_t)p.Qp * DP * 4)) return rc;
+  if (int rc = ensure(c->qn, (size_t)p.Qp * 8)) return rc;
+  if (int rc = ensure(c->q16, (size_t)p.Qp * DP * 2)) return rc;
+  PrepClear clr{};
+  if (p.path != SearchPath::Generic) {
+    if (int rc = size_buffers(c, p)) return rc;
+    clr = PrepClear{(int32_t*)c->counters.p, (int32_t*)c->cand_cnt.p, (uint32_t*)c->theta.p};
+  }
+  return launch_prep(qsrc, q.nq, D, DP, p.Qp, (float*)c->q32.p, (double*)c->qn.p, (_Float16*)c->q16.p, q.s, clr);
+}
+
+// K7's arguments for the main scan; the sample pass and K7c launch it with the changes they name.
+ScanParams scan_params(const Search& q, const SearchPlan& p) {
+  const mrag_knn_index* ix = q.ix;
+  const SearchCtx* c = q.c;
+  ScanParams sp{};
+  sp.x16 = (const _Float16*)ix->x16.p;
+  sp.labels = (const int32_t*)ix->labels.p;
+  sp.q16 = (const _Float16*)c->q16.p;
+  sp.ntiles = p.ntiles;
+  sp.qgroups = p.qgroups;
+  sp.splits = p.S;
+  sp.Qp = (int)p.Qp;
+  sp.label_filter = q.label_filter;
+  sp.part_s = (float*)c->part_s.p;
+  sp.part_i = (int32_t*)c->part_i.p;
+  sp.fail_list = (const int32_t*)c->fail_list.p;
+  sp.fail_cnt = (const int32_t*)c->counters.p;
+  sp.thresh = (const float*)c->thresh.p;
+  sp.cand_cnt = (int32_t*)c->cand_cnt.p;
+  sp.theta = (uint32_t*)c->theta.p;
+  sp.sample_tiles = p.sample_tiles;
+  sp.sample_stride = p.stride;
+  sp.k = q.k;
+  sp.part_tau = p.path == SearchPath::V3 ? (float*)c->part_tau.p : nullptr;
+  sp.rec = p.counting ? (uint32_t*)c->rec.p : nullptr;
+  sp.rec_keep = p.rec_keep;
+  sp.skip_magic = p.skip_magic;
+  return sp;
+}
+
+ResolveParams resolve_params(const Search& q, const SearchPlan& p, const ScanParams& sp) {
+  ResolveParams rp{};
+  rp.rec = sp.rec;
+  rp.idmask = ~sp.rec_keep;
+  rp.splits = p.S;
+  rp.Qp = (int)p.Qp;
+  rp.k = q.k;
+  rp.DP = q.ix->DP;
+  rp.tile_step = p.S * p.stride;
+  rp.label_filter = q.label_filter;
+  rp.x16 = sp.x16;
+  rp.q16 = sp.q16;
+  rp.labels = sp.labels;
+  rp.theta = sp.theta;
+  rp.part_s = sp.part_s;
+  rp.part_i = sp.part_i;
+  rp.part_tau = sp.part_tau;
+  return rp;
+}
+
+MergeParams merge_params(const Search& q, const SearchPlan& p) {
+  const mrag_knn_index* ix = q.ix;
+  const SearchCtx* c = q.c;
+  MergeParams mp{};
+  mp.part_s = (float*)c->part_s.p;
+  mp.part_i = (int32_t*)c->part_i.p;
+  mp.splits = p.S + p.SX;
+  mp.scan_splits = p.S;
+  mp.KL = p.KL;
+  mp.Qp = (int)p.Qp;
+  mp.nq = (int)q.nq;
+  mp.k = q.k;
+  mp.M = p.M;
+  mp.R = p.R;
+  mp.Mp = p.Mp;
+  mp.q32 = (const float*)c->q32.p;
+  mp.qn = (const double*)c->qn.p;
+  mp.x32 = (const float*)ix->x32.p;
+  mp.xn = (const double*)ix->xn.p;
+  mp.D = ix->D;
+  mp.DP = ix->DP;
+  mp.out_s = q.os;
+  mp.out_s64 = q.os64;
+  mp.out_r = q.orr;
+  mp.row_offset = q.row_offset;
+  mp.thresh = (float*)c->thresh.p;
+  mp.fail_list = (int32_t*)c->fail_list.p;
+  mp.fail_cnt = (int32_t*)c->counters.p;
+  mp.theta = (const uint32_t*)c->theta.p;
+  mp.part_tau = p.path == SearchPath::V3 ? (float*)c->part_tau.p : nullptr;
+  mp.host_fail = c->host_fail;
+  return mp;
+}
+
+FinalParams final_params(const Search& q, const CollectPlan& cp) {
+  const mrag_knn_index* ix = q.ix;
+  const SearchCtx* c = q.c;
+  FinalParams fp{};
+  fp.fail_list = (const int32_t*)c->fail_list.p;
+  fp.fail_cnt = (const int32_t*)c->counters.p;
+  fp.cand_cnt = (int32_t*)c->cand_cnt.p;
+  fp.cand = (int32_t*)c->cand.p;
+  fp.ccap = cp.ccap;
+  fp.scratch = (double*)c->scratch.p;
+  fp.q32 = (const float*)c->q32.p;
+  fp.qn = (const double*)c->qn.p;
+  fp.x32 = (const float*)ix->x32.p;
+  fp.xn = (const double*)ix->xn.p;
+  fp.D = ix->D;
+  fp.DP = ix->DP;
+  fp.k = q.k;
+  fp.out_s = q.os;
+  fp.out_s64 = q.os64;
+  fp.out_r = q.orr;
+  fp.row_offset = q.row_offset;
+  fp.overflow = (int32_t*)c->counters.p + 1;
+  return fp;
+}
+
+mrag_knn::GenericSearch generic_args(const Search& q) {
+  const mrag_knn_index* ix = q.ix;
+  const SearchCtx* c = q.c;
+  mrag_knn::GenericSearch ga{};
+  ga.x16 = (const _Float16*)ix->x16.p;
+  ga.x32 = (const float*)ix->x32.p;
+  ga.xn = (const double*)ix->xn.p;
+  ga.labels = (const int32_t*)ix->labels.p;
+  ga.n = ix->n;
+  ga.D = ix->D;
+  ga.DP = ix->DP;
+  ga.q16 = (const _Float16*)c->q16.p;
+  ga.q32 = (const float*)c->q32.p;
+  ga.qn = (const double*)c->qn.p;
+  ga.nq = (int)q.nq;
+  ga.k = q.k;
+  ga.label_filter = q.label_filter;
+  ga.row_offset = q.row_offset;
+  ga.out_s = q.os;
+  ga.out_s64 = q.os64;
+  ga.out_r = q.orr;
+  return ga;
+}
+
+// Sample stage (plan.sampled): the seed-only pass (MODE 1) and theta_init, or the counting pass
+// (MODE 2) and the resolve kernel. Both read the main scan's arguments; neither skips tiles.
+int sample_stage(const Search& q, const SearchPlan& p, ScanParams sp) {
+  sp.skip_magic = 0;
+  const dim3 sgrid((unsigned)(p.qgroups * p.S));
+  hipLaunchKernelGGL(get_scan3(q.ix->DP, p.counting ? 2 : 1, p.qb), sgrid, dim3(SCAN2_THREADS), 0, q.s, sp);
+  MRAG_CHECK_LAUNCH();
+  if (p.counting)
+    hipLaunchKernelGGL(sample_resolve_kernel, dim3((unsigned)q.nq), dim3(64), 0, q.s, resolve_params(q, p, sp));
+  else
+    hipLaunchKernelGGL(theta_init_kernel, dim3((unsigned)q.nq), dim3(64), 0, q.s, (const float*)sp.part_s, 4 * p.S,
+                       (int)p.Qp, q.k, sp.theta);
+  MRAG_CHECK_LAUNCH();
+  return MRAG_OK;
+}
+
+// Scan + K8 stage: the main scan (timed when profiling), K8, and the number of queries K8 could
+// not certify, read back on the host.
+int scan_merge_stage(const Search& q, const SearchPlan& p, const ScanParams& sp, scan_fn scan,
+                     int64_t* uncertified) {
+  mrag_knn_index* ix = q.ix;
+  SearchCtx* c = q.c;
+  const bool v3 = p.path == SearchPath::V3;
+  if (q.profile) MRAG_HIP(hipEventRecord(c->ev0, q.s));
+  hipLaunchKernelGGL(scan, dim3((unsigned)(p.qgroups * p.S)), dim3(v3 ? SCAN2_THREADS : SCAN_THREADS), 0, q.s, sp);
+  MRAG_CHECK_LAUNCH();
+  if (q.profile) MRAG_HIP(hipEventRecord(c->ev1, q.s));
+
+  __atomic_store_n(c->host_fail, 0, __ATOMIC_RELAXED);  // this context's previous search has completed
+  auto merge = p.sel == 1 ? knn_merge_kernel<1> : p.sel == 2 ? knn_merge_kernel<2> : knn_merge_kernel<0>;
+  hipLaunchKernelGGL(merge, dim3((unsigned)q.nq), dim3(MERGE_THREADS), p.merge_lds, q.s, merge_params(q, p));
+  MRAG_CHECK_LAUNCH();
+
+  // The failure count after K8: a failing query also raises the context's coherent host word,
+  // so the common search (every query certified) ends with the stream wait alone and launches
+  // nothing more; the count is copied back only when the word is set (the 8-byte copy was a
+  // 4.4 us kernel per search)
+  if (int rc = wait_stream(c, q.s)) return rc;
+  if (__atomic_load_n(c->host_fail, __ATOMIC_ACQUIRE)) {
+    MRAG_HIP(hipMemcpyAsync(c->host_counters, c->counters.p, 8, hipMemcpyDeviceToHost, q.s));
+    if (int rc = wait_stream(c, q.s)) return rc;
+  } else {
+    c->host_counters[0] = 0;
+  }
+  if (q.profile) {
+    float ms = 0.f;
+    MRAG_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    std::lock_guard<std::mutex> lk(ix->pool_mu);
+    ix->scan_ms += ms;
+    ix->scan_launches++;
+  }
+  *uncertified = c->host_counters[0];
+  return MRAG_OK;
+}
+
+// Collect stage, for the queries K8 could not certify: K7c collects every row that can reach
+// their top-k, K10 rescores and selects; a query that collects more than ccap rows sends the
+// whole batch to K7g.
+int collect_stage(const Search& q, const SearchPlan& p, ScanParams sp, scan_fn collect, SearchStats& st) {
+  SearchCtx* c = q.c;
+  const CollectPlan cp = plan_collect(st.uncertified, p);
+  if (int rc = ensure(c->cand, (size_t)p.Qp * cp.ccap * 4)) return rc;
+  if (int rc = ensure(c->scratch, (size_t)p.Qp * cp.ccap * 8)) return rc;
+  sp.cand = (int32_t*)c->cand.p;
+  sp.ccap = cp.ccap;
+  sp.qgroups = cp.cgroups;
+  sp.splits = cp.Sc;
+  st.info[2] = cp.cgroups;
+  st.info[3] = cp.Sc;
+  st.info[4] = cp.ccap;
+  st.info[5] = (int32_t)st.uncertified;
+  hipLaunchKernelGGL(collect, dim3((unsigned)(cp.cgroups * cp.Sc)), dim3(SCAN_THREADS), 0, q.s, sp);
+  MRAG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(knn_final_kernel, dim3((unsigned)st.uncertified), dim3(MERGE_THREADS), (size_t)q.ix->DP * 4, q.s,
+                     final_params(q, cp));
+  MRAG_CHECK_LAUNCH();
+  MRAG_HIP(hipMemcpyAsync(c->host_counters, c->counters.p, 8, hipMemcpyDeviceToHost, q.s));
+  if (int rc = wait_stream(c, q.s)) return rc;
+  st.info[6] = c->host_counters[1];
+  if (c->host_counters[1] != 0) {
+    st.retries = 1;
+    if (int rc = mrag_knn::search_generic(generic_args(q), c->gws, q.s, nullptr)) return rc;
+  }
+  return MRAG_OK;
+}
+
+// The fused search (v3 or v1 scan, K8, collect when needed) along its plan.
+int search_fused(const Search& q, const SearchPlan& p, SearchStats& st) {
+  const int DP = q.ix->DP;
+  const scan_fn scan = p.path == SearchPath::V3 ? get_scan3(DP, 0, p.qb) : get_scan(DP, p.KL, false);
+  const scan_fn collect = get_scan(DP, 8, true);
+  if (!scan || !collect) return mrag::fail(MRAG_ERR_UNSUPPORTED, "no scan kernel for DP=%d", DP);
+  st.info[0] = p.S;
+  st.info[1] = (int32_t)p.Qp;
+  st.info[7] = p.KL;
+  if (int rc = stage_queries(q, p)) return rc;
+  const ScanParams sp = scan_params(q, p);
+  if (p.sampled)
+    if (int rc = sample_stage(q, p, sp)) return rc;
+  if (int rc = scan_merge_stage(q, p, sp, scan, &st.uncertified)) return rc;
+  if (st.uncertified > 0) return collect_stage(q, p, sp, collect, st);
   return MRAG_OK;
 }
 
@@ -2021,17 +2300,9 @@ int mrag_knn_create(int32_t dim, int32_t device, mrag_knn_index** out) {
 
 int mrag_knn_destroy(mrag_knn_index* ix) {
   if (!ix) return MRAG_OK;
-  {
-    mrag::DeviceGuard g(ix->device);
-    (void)hipStreamSynchronize(ix->stream);
-    std::unique_lock<std::shared_mutex> wl(ix->rw);  // no search in flight
-    for (DevBuf* b : {&ix->x16, &ix->x32, &ix->xn, &ix->labels, &ix->stage_rows, &ix->stage_labels, &ix->rowlist})
-      release(*b);
-    for (SearchCtx* c : ix->ctx_all) ctx_free_all(c);
-    ix->ctx_all.clear();
-    ix->ctx_free.clear();
-    if (ix->stream) (void)hipStreamDestroy(ix->stream);
-  }
+  mrag::DeviceGuard g(ix->device);  // the buffers, contexts and the stream are freed on their device
+  (void)hipStreamSynchronize(ix->stream);
+  { std::unique_lock<std::shared_mutex> wl(ix->rw); }  // no search in flight
   delete ix;
   return MRAG_OK;
 }
@@ -2149,7 +2420,6 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
   // destroyed before the lease and the shared lock: an error after the first launch drains s
   // before the context returns to the pool and mutations may free the corpus buffers
   mrag::StreamDrain drain(s);
-  const int D = ix->D, DP = ix->DP;
   const int64_t nout = nq * k;
 
   // output destinations (device)
@@ -2166,295 +2436,22 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
       os64 = (double*)c->out_s64.p;
     }
   }
-  int64_t uncertified = 0, retries = 0;
-  int32_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-  auto generic_args = [&]() {
-    mrag_knn::GenericSearch ga{};
-    ga.x16 = (const _Float16*)ix->x16.p;
-    ga.x32 = (const float*)ix->x32.p;
-    ga.xn = (const double*)ix->xn.p;
-    ga.labels = (const int32_t*)ix->labels.p;
-    ga.n = ix->n;
-    ga.D = D;
-    ga.DP = DP;
-    ga.q16 = (const _Float16*)c->q16.p;
-    ga.q32 = (const float*)c->q32.p;
-    ga.qn = (const double*)c->qn.p;
-    ga.nq = (int)nq;
-    ga.k = k;
-    ga.label_filter = label_filter;
-    ga.row_offset = row_offset;
-    ga.out_s = os;
-    ga.out_s64 = os64;
-    ga.out_r = orr;
-    return ga;
-  };
-
-  if (ix->n == 0) {
-    hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, os, os64,
-                       orr, nout);
-    MRAG_CHECK_LAUNCH();
-  } else if (DP > 512 || k > MAX_K) {
-    // K7g (knn_generic.hip): widths and depths the fused scan does not instantiate
-    const float* qsrc = queries;
-    if (host) {
-      if (int rc = ensure(c->qin, (size_t)nq * D * 4)) return rc;
-      MRAG_HIP(hipMemcpyAsync(c->qin.p, queries, (size_t)nq * D * 4, hipMemcpyHostToDevice, s));
-      qsrc = (const float*)c->qin.p;
-    }
-    if (int rc = ensure(c->q32, (size_t)nq * DP * 4)) return rc;
-    if (int rc = ensure(c->qn, (size_t)nq * 8)) return rc;
-    if (int rc = ensure(c->q16, (size_t)nq * DP * 2)) return rc;
-    if (int rc = launch_prep(qsrc, nq, D, DP, nq, (float*)c->q32.p, (double*)c->qn.p, (_Float16*)c->q16.p, s))
-      return rc;
-    if (int rc = mrag_knn::search_generic(generic_args(), c->gws, s, nullptr)) return rc;
-  } else {
-    // v3 (MFMA 16x16x32, 64 queries per wave, per-lane lists of 6 folded to 8 per split) unless
-    // k is deep enough to want longer per-lane lists (v1). For 32 < k <= 64 the union of the S
-    // split lists still holds S * 8 >= k + 32 candidates at the batch sizes that matter, and the
-    // certificate sends any query whose top-k a list could not hold to the collect pass.
-    const bool use_v3 = k <= 64;
-    const int qb = use_v3 ? scan3_qb(nq) : 4;
-    const int qpg = use_v3 ? 64 * qb : QPG;  // queries per scan workgroup
-    // query slots: v3 reads every slot of its query group (no lane guard), so pad to a whole
-    // group; padding rows are zero (prep) and never reach the output
-    const int64_t qpad = use_v3 ? qpg : QPW;
-    const int64_t Qp = (nq + qpad - 1) / qpad * qpad;
-    const int qgroups = (int)((Qp + qpg - 1) / qpg);
-    const int ntiles = (int)((ix->n + TILE_ROWS - 1) / TILE_ROWS);
-    const int KL = use_v3 ? 8 : kl_for(k, DP);
-    int S = std::max(1, 256 / qgroups);
-    S = std::min(S, ntiles);
-    S = std::min(S, MAX_MERGE_ENTRIES / KL);
-    if (S >= 8) S &= ~7;
-    // Sample pass (v3, 256-query groups, when every split has >= 4 * stride tiles): seed only, or
-    // counting (its rows reach K8 through XLISTS extra lists) while the group ids fit the record
-    const int min_tiles = ntiles / S;
-    const int stride = sample_stride_for(k);
-    const bool sampled = use_v3 && qb == 4 && min_tiles >= 4 * stride;
-    const int max_sample_tiles = ((ntiles + S - 1) / S + stride - 1) / stride;
-    int idbits = 2;
-    while ((1 << idbits) < 4 * max_sample_tiles) ++idbits;
-    const bool counting = sampled && counting_sample_for(k) && idbits <= REC_ID_BITS_MAX;
-    const int SX = counting ? XLISTS : 0;
-    const int M = std::min<int>(k + 32, S * KL);
-    const int R = (int)next_pow2((int64_t)(S + SX) * KL);
-    const int Mp = (int)next_pow2(std::max(M, 2));
-    info[0] = S;
-    info[1] = (int32_t)Qp;
-    info[7] = KL;
-
-    const float* qsrc = queries;
-    if (host) {
-      if (int rc = ensure(c->qin, (size_t)nq * D * 4)) return rc;
-      MRAG_HIP(hipMemcpyAsync(c->qin.p, queries, (size_t)nq * D * 4, hipMemcpyHostToDevice, s));
-      qsrc = (const float*)c->qin.p;
-    }
-    if (int rc = ensure(c->q32, (size_t)Qp * DP * 4)) return rc;
-    if (int rc = ensure(c->qn, (size_t)Qp * 8)) return rc;
-    if (int rc = ensure(c->q16, (size_t)Qp * DP * 2)) return rc;
-    if (int rc = ensure(c->part_s, (size_t)(S + SX) * Qp * KL * 4)) return rc;
-    if (int rc = ensure(c->part_i, (size_t)(S + SX) * Qp * KL * 4)) return rc;
-    if (int rc = ensure(c->thresh, (size_t)Qp * 4)) return rc;
-    if (int rc = ensure(c->fail_list, (size_t)Qp * 4)) return rc;
-    if (int rc = ensure(c->counters, 16)) return rc;
-    if (int rc = ensure(c->cand_cnt, (size_t)Qp * 4)) return rc;
-    if (int rc = ensure(c->theta, (size_t)Qp * 4)) return rc;
-    if (use_v3)
-      if (int rc = ensure(c->part_tau, (size_t)(S + SX) * Qp * 4)) return rc;
-    if (counting)
-      if (int rc = ensure(c->rec, (size_t)S * Qp * 16 * 4)) return rc;
-
-    if (int rc = launch_prep(qsrc, nq, D, DP, Qp, (float*)c->q32.p, (double*)c->qn.p, (_Float16*)c->q16.p, s,
-                             PrepClear{(int32_t*)c->counters.p, (int32_t*)c->cand_cnt.p, (uint32_t*)c->theta.p}))
-      return rc;
-
-    ScanParams sp{};
-    sp.theta = (uint32_t*)c->theta.p;
-
-    sp.x16 = (const _Float16*)ix->x16.p;
-    sp.labels = (const int32_t*)ix->labels.p;
-    sp.q16 = (const _Float16*)c->q16.p;
-    sp.ntiles = ntiles;
-    sp.qgroups = qgroups;
-    sp.splits = S;
-    sp.Qp = (int)Qp;
-    sp.label_filter = label_filter;
-    sp.part_s = (float*)c->part_s.p;
-    sp.part_i = (int32_t*)c->part_i.p;
-    sp.fail_list = (const int32_t*)c->fail_list.p;
-    sp.fail_cnt = (const int32_t*)c->counters.p;
-    sp.thresh = (const float*)c->thresh.p;
-    sp.cand_cnt = (int32_t*)c->cand_cnt.p;
-    sp.k = k;
-    sp.part_tau = use_v3 ? (float*)c->part_tau.p : nullptr;
-
-    const scan_fn scan = use_v3 ? get_scan3(DP, 0, qb) : get_scan(DP, KL, false);
-    const scan_fn collect = get_scan(DP, 8, true);
-    if (!scan || !collect) return mrag::fail(MRAG_ERR_UNSUPPORTED, "no scan kernel for DP=%d", DP);
-    const dim3 sgrid((unsigned)(qgroups * S));
-    // Sample pre-pass (v3, when every split has >= 4 * SAMPLE_STRIDE tiles): seeds the shared
-    // threshold near the k-th best so the main scan's list insertions stay rare. Four maxima per
-    // (split, query), one per lane group (merging them in pairs, the round-1 seed, measured 0.2 %
-    // slower in the main scan); stride 16 (32: +5 %, 64: +14 %, none: +70 % scan time). K7s
-    // (qb == 1) streams at the HBM rate, where the pre-pass costs more than the inserts it saves
-    // (Q = 1: 0.270 -> 0.247 ms without it, notes/knn_scan_experiments.md).
-    // The counting pass (k <= 16) keeps a per-lane record instead of the maxima; the resolve
-    // kernel seeds the threshold from it and lists the sampled rows above the seed, and the main
-    // scan walks the other tiles only.
-    sp.sample_stride = stride;  // MODE 0 reads it too (skip_sampled)
-    if (sampled) {
-      sp.sample_tiles = min_tiles / stride;
-      if (counting) {
-        sp.rec = (uint32_t*)c->rec.p;
-        sp.rec_keep = ~((1u << idbits) - 1u);
-      }
-      hipLaunchKernelGGL(get_scan3(DP, counting ? 2 : 1, qb), sgrid, dim3(SCAN2_THREADS), 0, s, sp);
+  const Search q{ix, c, s, queries, host, nq, k, label_filter, row_offset, os, os64, orr, profile};
+  const SearchPlan plan = plan_search(ix->n, nq, k, ix->DP);
+  SearchStats st;
+  switch (plan.path) {
+    case SearchPath::Empty:
+      hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, os, os64, orr,
+                         nout);
       MRAG_CHECK_LAUNCH();
-      if (counting) {
-        ResolveParams rp{};
-        rp.rec = sp.rec;
-        rp.idmask = ~sp.rec_keep;
-        rp.splits = S;
-        rp.Qp = (int)Qp;
-        rp.k = k;
-        rp.DP = DP;
-        rp.tile_step = S * stride;
-        rp.label_filter = label_filter;
-        rp.x16 = sp.x16;
-        rp.q16 = sp.q16;
-        rp.labels = sp.labels;
-        rp.theta = sp.theta;
-        rp.part_s = sp.part_s;
-        rp.part_i = sp.part_i;
-        rp.part_tau = sp.part_tau;
-        hipLaunchKernelGGL(sample_resolve_kernel, dim3((unsigned)nq), dim3(64), 0, s, rp);
-        sp.skip_magic = (uint32_t)((1ull << 32) / (uint64_t)(stride - 1) + 1);
-      } else {
-        hipLaunchKernelGGL(theta_init_kernel, dim3((unsigned)nq), dim3(64), 0, s, (const float*)sp.part_s, 4 * S,
-                           (int)Qp, k, sp.theta);
-      }
-      MRAG_CHECK_LAUNCH();
-    }
-    if (profile) MRAG_HIP(hipEventRecord(c->ev0, s));
-    hipLaunchKernelGGL(scan, sgrid, dim3(use_v3 ? SCAN2_THREADS : SCAN_THREADS), 0, s, sp);
-    MRAG_CHECK_LAUNCH();
-    if (profile) MRAG_HIP(hipEventRecord(c->ev1, s));
-
-    MergeParams mp{};
-    mp.part_s = sp.part_s;
-    mp.part_i = sp.part_i;
-    mp.splits = S + SX;
-    mp.scan_splits = S;
-    mp.KL = KL;
-    mp.Qp = (int)Qp;
-    mp.nq = (int)nq;
-    mp.k = k;
-    mp.M = M;
-    mp.R = R;
-    mp.Mp = Mp;
-    mp.q32 = (const float*)c->q32.p;
-    mp.qn = (const double*)c->qn.p;
-    mp.x32 = (const float*)ix->x32.p;
-    mp.xn = (const double*)ix->xn.p;
-    mp.D = D;
-    mp.DP = DP;
-    mp.out_s = os;
-    mp.out_s64 = os64;
-    mp.out_r = orr;
-    mp.row_offset = row_offset;
-    mp.thresh = (float*)c->thresh.p;
-    mp.fail_list = (int32_t*)c->fail_list.p;
-    mp.fail_cnt = (int32_t*)c->counters.p;
-    mp.theta = (const uint32_t*)c->theta.p;
-    mp.part_tau = sp.part_tau;
-    mp.host_fail = c->host_fail;
-    __atomic_store_n(c->host_fail, 0, __ATOMIC_RELAXED);  // this context's previous search has completed
-    // K8 key selection: the best M + 1 keys (the M candidates and the first one left out) by
-    // the register top-64P fold when they fit, else the full bitonic sort (40.6 -> 36.5 us per
-    // 1000-query search for the fold)
-    const int sel = M + 1 <= 64 ? 1 : (M + 1 <= 128 ? 2 : 0);
-    mp.R = sel ? std::max(R, 4 * 64 * sel) : R;  // the fold parks four waves' top-64P in keys[]
-    const size_t msh = (size_t)mp.R * 8 + (size_t)Mp * 12 + (size_t)DP * 4 + 64;
-    auto merge = sel == 1 ? knn_merge_kernel<1> : sel == 2 ? knn_merge_kernel<2> : knn_merge_kernel<0>;
-    hipLaunchKernelGGL(merge, dim3((unsigned)nq), dim3(MERGE_THREADS), msh, s, mp);
-    MRAG_CHECK_LAUNCH();
-
-    // The failure count after K8: a failing query also raises the context's coherent host word,
-    // so the common search (every query certified) ends with the stream wait alone and the count
-    // is copied back only when the word is set (the 8-byte copy was a 4.4 us kernel per search);
-    // the common search launches nothing more; otherwise K7c's grid is sized to the failing queries alone, with
-    // more splits than the main scan (one failing query over the main scan's 64 splits is one
-    // 8-wave workgroup per split, latency-bound on its own LDS-DMA round trips: 0.3 ms over
-    // 512k rows, notes/knn_scan_experiments.md)
-    if (int rc = wait_stream(c, s)) return rc;
-    if (__atomic_load_n(c->host_fail, __ATOMIC_ACQUIRE)) {
-      MRAG_HIP(hipMemcpyAsync(c->host_counters, c->counters.p, 8, hipMemcpyDeviceToHost, s));
-      if (int rc = wait_stream(c, s)) return rc;
-    } else {
-      c->host_counters[0] = 0;
-    }
-    if (profile) {
-      float ms = 0.f;
-      MRAG_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-      std::lock_guard<std::mutex> lk(ix->pool_mu);
-      ix->scan_ms += ms;
-      ix->scan_launches++;
-    }
-    uncertified = c->host_counters[0];
-    if (uncertified > 0) {
-      // per-slot collect capacity of this search (K7c/K10 for the uncertified queries): at
-      // most 4096 rows and 64M slots in all; a query that collects more (a run of more than
-      // ccap near-duplicates within eps of its k-th score) sends the batch to K7g below,
-      // whose per-query storage is sized from a histogram — nothing grows across searches
-      const int ccap = (int)std::max<int64_t>(256, std::min<int64_t>(4096, ((int64_t)64 << 20) / Qp));
-      if (int rc = ensure(c->cand, (size_t)Qp * ccap * 4)) return rc;
-      if (int rc = ensure(c->scratch, (size_t)Qp * ccap * 8)) return rc;
-      sp.cand = (int32_t*)c->cand.p;
-      sp.ccap = ccap;
-      // K7c: QPG failing queries per workgroup, about 1024 workgroups in all
-      const int cgroups = (int)((uncertified + QPG - 1) / QPG);
-      int Sc = std::max(S, 1024 / cgroups);
-      Sc = std::min(Sc, ntiles);
-      if (Sc >= 8) Sc &= ~7;
-      sp.qgroups = cgroups;
-      sp.splits = Sc;
-      info[2] = cgroups;
-      info[3] = Sc;
-      info[4] = ccap;
-      info[5] = (int32_t)uncertified;
-      hipLaunchKernelGGL(collect, dim3((unsigned)(cgroups * Sc)), dim3(SCAN_THREADS), 0, s, sp);
-      MRAG_CHECK_LAUNCH();
-      FinalParams fp{};
-      fp.fail_list = sp.fail_list;
-      fp.fail_cnt = sp.fail_cnt;
-      fp.cand_cnt = sp.cand_cnt;
-      fp.cand = sp.cand;
-      fp.ccap = ccap;
-      fp.scratch = (double*)c->scratch.p;
-      fp.q32 = mp.q32;
-      fp.qn = mp.qn;
-      fp.x32 = mp.x32;
-      fp.xn = mp.xn;
-      fp.D = D;
-      fp.DP = DP;
-      fp.k = k;
-      fp.out_s = os;
-      fp.out_s64 = os64;
-      fp.out_r = orr;
-      fp.row_offset = row_offset;
-      fp.overflow = (int32_t*)c->counters.p + 1;
-      hipLaunchKernelGGL(knn_final_kernel, dim3((unsigned)uncertified), dim3(MERGE_THREADS), (size_t)DP * 4, s, fp);
-      MRAG_CHECK_LAUNCH();
-      MRAG_HIP(hipMemcpyAsync(c->host_counters, c->counters.p, 8, hipMemcpyDeviceToHost, s));
-      if (int rc = wait_stream(c, s)) return rc;
-      info[6] = c->host_counters[1];
-      if (c->host_counters[1] != 0) {
-        retries = 1;
-        if (int rc = mrag_knn::search_generic(generic_args(), c->gws, s, nullptr)) return rc;
-      }
-    }
+      break;
+    case SearchPath::Generic:
+      if (int rc = stage_queries(q, plan)) return rc;
+      if (int rc = mrag_knn::search_generic(generic_args(q), c->gws, s, nullptr)) return rc;
+      break;
+    default:
+      if (int rc = search_fused(q, plan, st)) return rc;
   }
 
   if (host) {
@@ -2465,10 +2462,10 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
   if (int rc = wait_stream(c, s)) return rc;
   drain.armed = false;
   std::lock_guard<std::mutex> lk(ix->pool_mu);
-  ix->last_uncertified = uncertified;
-  ix->last_retries = retries;
+  ix->last_uncertified = st.uncertified;
+  ix->last_retries = st.retries;
   ix->last_ctx = c;
-  std::copy(info, info + 8, ix->last_info);
+  std::copy(st.info, st.info + 8, ix->last_info);
   return MRAG_OK;
 }
 

@@ -7,8 +7,9 @@ Also the band cases written for a K8 that rescores only candidates with approx >
 inside and outside sampled tiles, so the rows returned and their order depend on every one of
 them being rescored; and a query with fewer than k matching rows.
 
-Shapes: 1000 queries (4 query groups, 64 splits) over 270k x 128 is the smallest corpus on which
-the sample pre-pass seeds the threshold; 140k x 512 is the second instantiation. The oracle is
+Shapes: 1000 queries (4 query groups, 64 splits) over 270k rows, so that every split holds the
+64 tiles the sample pass needs, at 128 dims and at 512 (the second instantiation);
+tests/test_knn_plan_cpu.py asserts that these shapes take the counting pass. The oracle is
 run on the planted queries and a few plain ones only (a query's result does not depend on the
 rest of the batch), which keeps a case to a few seconds.
 """
@@ -76,7 +77,7 @@ def _corpus(n, dim, k, seed):
     return x, lab, q
 
 
-@pytest.fixture(scope="module", params=[(270_000, 128, 10), (140_000, 512, 12)], ids=["dp128_k10", "dp512_k12"])
+@pytest.fixture(scope="module", params=[(270_000, 128, 10), (270_000, 512, 12)], ids=["dp128_k10", "dp512_k12"])
 def banded(request, cuda):
     from app.vector_store import FlatIndex
 
