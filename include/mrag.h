@@ -110,6 +110,21 @@ int mrag_knn_search(mrag_knn_index* index, const float* queries, int64_t nq, int
                     int32_t label_filter, int64_t row_offset, float* out_scores,
                     double* out_scores64, int64_t* out_rows, int32_t ptr_kind, void* stream);
 
+/* The same search with one label filter per query: label_filters int32 [nq],
+ * host or device memory according to ptr_kind like the other data pointers,
+ * label_filters[i] a label >= 0 or MRAG_LABEL_ANY. Query i gets the k best
+ * rows among those its own filter admits (a batch of different users' queries
+ * in one scan; the rows are masked per query inside the scan kernels, before
+ * any candidate is kept). Everything else is mrag_knn_search's contract: exact
+ * f64 cosine in (score desc, row asc) order, -inf / -1 past the matching rows,
+ * tombstones never match, mrag_knn_last_stats, thread safety.
+ * An entry below MRAG_LABEL_ANY: a host array is checked before any launch and
+ * the call returns MRAG_ERR_ARG; a device array is not read on the host, and
+ * such an entry matches no row (that query's slots are all -inf / -1). */
+int mrag_knn_search_labels(mrag_knn_index* index, const float* queries, int64_t nq, int32_t k,
+                           const int32_t* label_filters, int64_t row_offset, float* out_scores,
+                           double* out_scores64, int64_t* out_rows, int32_t ptr_kind, void* stream);
+
 /* Statistics of the last search on this handle: number of queries whose fp16
  * candidate pass could not be certified exact and went through the
  * threshold-collect pass, and how many collect retries overflowed. */

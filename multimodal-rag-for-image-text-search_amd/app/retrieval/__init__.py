@@ -10,7 +10,7 @@ reference's z-score fusion. Results for query i equal ``retrieve_text(user, q_i)
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
@@ -23,8 +23,23 @@ def _store():
     return r._LANCEDB_STORE, r._METADATA_STORE
 
 
-def search_batch(modality: str, user_id: str, query_vecs: np.ndarray, top_k: int) -> List[List[Dict[str, Any]]]:
-    """Raw hits ({chunk_id, score, meta}) for every row of ``query_vecs``, one GPU launch."""
+def _user_list(user_id: Union[str, Sequence[str]], n: int) -> Optional[List[str]]:
+    """None for one user id (a str); else the per-query user ids, checked against n queries."""
+    if isinstance(user_id, str):
+        return None
+    users = list(user_id)
+    if len(users) != n:
+        raise ValueError(f"user_id must be a str or hold one user per query ({n}), got {len(users)}")
+    return users
+
+
+def search_batch(modality: str, user_id: Union[str, Sequence[str]], query_vecs: np.ndarray,
+                 top_k: int) -> List[List[Dict[str, Any]]]:
+    """Raw hits ({chunk_id, score, meta}) for every row of ``query_vecs``, one GPU launch.
+
+    ``user_id`` is one user for the whole batch or a sequence of one user per query: a batch a
+    multi-user server collected from concurrent requests is still one scan, each query filtered
+    to its own user's rows (a user the table has never seen gets ``[]``)."""
     store, _ = _store()
     table = store._text_table if modality == "text" else store._image_table
     q = np.asarray(query_vecs, dtype=np.float32)
@@ -32,11 +47,18 @@ def search_batch(modality: str, user_id: str, query_vecs: np.ndarray, top_k: int
         q = q[None, :]
     norms = np.linalg.norm(q, axis=1, keepdims=True)
     q = np.where(norms > 0, q / np.where(norms > 0, norms, 1), q).astype(np.float32)
+    users = _user_list(user_id, len(q))
     with table.lock:
         table._sync()  # replay what any process committed since the last call
-        label = table.labels.get(user_id)
-        if table.index is None or label is None:
-            return [[] for _ in range(len(q))]
+        if users is None:
+            label = table.labels.get(user_id)
+            if table.index is None or label is None:
+                return [[] for _ in range(len(q))]
+        else:
+            # an unknown user maps to a label no row carries: their queries match nothing
+            label = np.array([table.labels.get(u, len(table.labels)) for u in users], dtype=np.int32)
+            if table.index is None or len(q) == 0:
+                return [[] for _ in range(len(q))]
         s, r = table.index.search(q, max(int(top_k), 1), label=label)
         out = []
         for i in range(len(q)):
@@ -59,11 +81,13 @@ def _branch_pool():
     return _BRANCH_POOL
 
 
-def retrieve_batch(user_id: str, queries: Sequence[str], top_k_text: Optional[int] = None,
+def retrieve_batch(user_id: Union[str, Sequence[str]], queries: Sequence[str], top_k_text: Optional[int] = None,
                    top_k_image: Optional[int] = None, rerank: Optional[bool] = None) -> List[List[Dict[str, Any]]]:
     """Fused text+image results per query, batched end to end = ``retrieve(user_id, q)``
     (app/ml/retrieve.py:103-117) for every q. ``rerank`` defaults to RERANK_ENABLED; the
     cross-encoder is ``retrieve._get_cross_encoder()`` (False -> no rerank, as retrieve).
+    ``user_id`` is one user or one per query (``search_batch``): result i then equals
+    ``retrieve_batch(user_id[i], [queries[i]], ...)[0]``.
 
     The image branch (CLIP text tower -> image search) runs in a worker thread beside the text
     branch (MiniLM -> text search): each native call returns to its own thread only, so the two
@@ -74,6 +98,7 @@ def retrieve_batch(user_id: str, queries: Sequence[str], top_k_text: Optional[in
     tk = top_k_text or settings.retrieval.index_topk_text
     ik = top_k_image or settings.retrieval.index_topk_image
     qs = list(queries)
+    _user_list(user_id, len(qs))  # a sequence of the wrong length: ValueError before any work
     if not qs:
         return []
 

@@ -120,13 +120,20 @@ class FlatIndex:
         self.set_labels(rows, LABEL_DELETED)
 
     # ------------------------------------------------------------------ search
-    def search(self, queries: ArrayLike, k: int, label: int = LABEL_ANY, row_offset: int = 0,
+    def search(self, queries: ArrayLike, k: int, label: Union[int, ArrayLike] = LABEL_ANY, row_offset: int = 0,
                with_f64: bool = False):
         """k best rows per query: ``(scores f32 [nq,k], rows int64 [nq,k][, scores f64])``.
 
+        ``label`` is one filter for the whole batch (an int) or one per query (an array or
+        tensor of ``nq`` int32 values, each a label >= 0 or ``LABEL_ANY``): query i then gets
+        the k best rows among those its own filter admits, in the same single scan
+        (``mrag_knn_search_labels``). An array whose entries are all equal takes the single-filter
+        search (the same result by definition, without the per-query mask's cost: DESIGN.md §3.2).
         Empty slots (fewer matching rows than k) have score ``-inf`` and row ``-1``.
         """
         k = int(k)
+        if not isinstance(label, (int, np.integer)):
+            return self._search_labels(queries, k, label, int(row_offset), with_f64)
         if _is_torch(queries):
             import torch
 
@@ -153,6 +160,59 @@ class FlatIndex:
         r = np.empty((nq, k), dtype=np.int64)
         s64 = np.empty((nq, k), dtype=np.float64) if with_f64 else None
         _native.call("mrag_knn_search", self._h, q.ctypes.data, nq, k, int(label), int(row_offset),
+                     s.ctypes.data, s64.ctypes.data if s64 is not None else None, r.ctypes.data,
+                     _native.MRAG_PTR_HOST, None)
+        return (s, r, s64) if with_f64 else (s, r)
+
+    def _search_labels(self, queries: ArrayLike, k: int, labels: ArrayLike, row_offset: int, with_f64: bool,
+                       group_equal: bool = True):
+        """``search`` with one label filter per query. ``group_equal=False`` keeps an array of
+        equal entries on the per-query entry point (measurements and kernel tests)."""
+        if _is_torch(queries):
+            import torch
+
+            q = queries.detach().to(dtype=torch.float32).contiguous()
+            if q.ndim == 1:
+                q = q.unsqueeze(0)
+            if q.shape[1] != self.dim:
+                raise ValueError(f"queries must be [nq, {self.dim}]")
+            nq = q.shape[0]
+            lab = torch.as_tensor(np.asarray(labels) if not _is_torch(labels) else labels)
+            lab = lab.detach().reshape(-1).to(device=q.device, dtype=torch.int32).contiguous()
+            if lab.shape[0] != nq:
+                raise ValueError(f"label must be an int or hold one filter per query ({nq}), got {lab.shape[0]}")
+            if nq:
+                lo, hi = (int(v) for v in torch.stack(torch.aminmax(lab)).tolist())  # one read-back for both checks
+                if lo < LABEL_ANY:
+                    raise ValueError("label filters must be labels >= 0 or LABEL_ANY")
+                if lo == hi and group_equal:
+                    return self.search(q, k, label=lo, row_offset=row_offset, with_f64=with_f64)
+            s = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+            r = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            s64 = torch.empty((nq, k), dtype=torch.float64, device=q.device) if with_f64 else None
+            _native.call("mrag_knn_search_labels", self._h, q.data_ptr(), nq, k, lab.data_ptr(), row_offset,
+                         s.data_ptr(), s64.data_ptr() if s64 is not None else None, r.data_ptr(),
+                         _native.MRAG_PTR_DEVICE, _stream_ptr(q))
+            return (s, r, s64) if with_f64 else (s, r)
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}], got {q.shape}")
+        nq = q.shape[0]
+        if _is_torch(labels):
+            labels = labels.detach().cpu().numpy()
+        lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
+        if lab.shape[0] != nq:
+            raise ValueError(f"label must be an int or hold one filter per query ({nq}), got {lab.shape[0]}")
+        if np.any(lab < LABEL_ANY):
+            raise ValueError("label filters must be labels >= 0 or LABEL_ANY")
+        if nq and group_equal and lab.min() == lab.max():
+            return self.search(q, k, label=int(lab[0]), row_offset=row_offset, with_f64=with_f64)
+        s = np.empty((nq, k), dtype=np.float32)
+        r = np.empty((nq, k), dtype=np.int64)
+        s64 = np.empty((nq, k), dtype=np.float64) if with_f64 else None
+        _native.call("mrag_knn_search_labels", self._h, q.ctypes.data, nq, k, lab.ctypes.data, row_offset,
                      s.ctypes.data, s64.ctypes.data if s64 is not None else None, r.ctypes.data,
                      _native.MRAG_PTR_HOST, None)
         return (s, r, s64) if with_f64 else (s, r)

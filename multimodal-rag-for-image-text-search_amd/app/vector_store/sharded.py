@@ -48,11 +48,12 @@ class ShardedFlatIndex:
         dist.all_gather(parts, t.contiguous(), group=self.group)
         return torch.stack(parts)
 
-    def search(self, queries, k: int, label: int = -1) -> Tuple:
-        """(scores f32 [nq,k], rows int64 [nq,k]) over the whole sharded corpus."""
+    def search(self, queries, k: int, label=-1) -> Tuple:
+        """(scores f32 [nq,k], rows int64 [nq,k]) over the whole sharded corpus; ``label`` is one
+        filter or one per query, as ``FlatIndex.search`` takes it."""
         return self.combine(self.search_local(queries, k, label=label), k)
 
-    def search_local(self, queries, k: int, label: int = -1) -> Tuple:
+    def search_local(self, queries, k: int, label=-1) -> Tuple:
         """Step 1 alone: this shard's exact top-k with global row ids (plus the f64 scores the
         merge orders by when world > 1). Safe to run from several host threads at once, each on
         its own stream (the library gives every search its own workspace)."""

@@ -88,7 +88,20 @@ struct ScanParams {
   uint32_t* rec;
   uint32_t rec_keep;
   uint32_t skip_magic;
+  // per-query label filters (the PQL kernel instances only): [Qp], one label >= 0, MRAG_LABEL_ANY
+  // or QLAB_NONE per query slot, indexed by the original query (K7c: fail_list's entry). Last, so
+  // the other fields keep their kernel-argument offsets.
+  const int32_t* qlab;
 };
+
+// A per-query filter that admits no row (padded query slots, invalid entries of a device array):
+// row labels are >= 0 or MRAG_LABEL_DELETED, never this.
+constexpr int32_t QLAB_NONE = INT32_MIN;
+// (lo, span) of a per-query filter L: a row label passes iff (uint32)label - lo <= span
+__device__ __forceinline__ uint32_t qlab_lo(int32_t L) {
+  return (uint32_t)(L >= 0 ? L : (L == MRAG_LABEL_ANY ? 0 : QLAB_NONE));
+}
+__device__ __forceinline__ uint32_t qlab_span(int32_t L) { return L == MRAG_LABEL_ANY ? 0x7fffffffu : 0u; }
 
 template <int KL>
 __device__ __forceinline__ void list_insert(float (&ls)[KL], int (&li)[KL], float s, int r) {
@@ -196,7 +209,11 @@ __device__ __forceinline__ float masked_max16(const f32x16& a, uint64_t lane_mas
 // mask from one ballot over the tile's labels, the max of each lane's 32 scores,
 // and ONE wave-level test against the lane's rejection threshold; the per-row list
 // insertion runs only when some lane of the wave has a score above its threshold.
-template <int DP, int KL, bool COLLECT>
+//
+// PQL (per-query labels): every lane masks its rows with its own query's filter, p.qlab[query],
+// where the other instances share one tile mask: lane_mask is built per lane from the tile's
+// labels in LDS, and row_ok / masked_max16 / rows_pass work on it unchanged.
+template <int DP, int KL, bool COLLECT, bool PQL = false>
 __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_kernel(ScanParams p) {
   constexpr int KSTEPS = DP / 16;
   constexpr int ROW_BYTES = DP * 2;
@@ -255,6 +272,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_kernel(ScanParams p) {
   float thr_collect = INFINITY;
   if constexpr (COLLECT) {
     if (lane_active) thr_collect = p.thresh[qrow];
+  }
+  // PQL: the lane's filter, looked up by the original query slot (K7c compacts the failing
+  // queries: qrow, not slot); lanes without a query admit nothing
+  uint32_t f_lo = 0u, f_span = 0u;
+  if constexpr (PQL) {
+    const int32_t L = lane_active ? p.qlab[qrow] : QLAB_NONE;
+    f_lo = qlab_lo(L);
+    f_span = qlab_span(L);
   }
 
   float ls[KL];
@@ -332,10 +357,29 @@ __global__ __launch_bounds__(SCAN_THREADS) void knn_scan_kernel(ScanParams p) {
       if (it + 1 < my_tiles) stage(cur ^ 1, tile + p.splits);
 
       // row validity of this tile: one label per lane -> 64-bit ballot (uniform)
-      const int lab = ((const int*)(smem + LBL_OFF + cur * TILE_ROWS * 4))[lane];
-      const bool lab_ok = (p.label_filter == MRAG_LABEL_ANY) ? (lab >= 0) : (lab == p.label_filter);
-      const uint64_t tile_mask = __ballot(lab_ok);
-      const uint64_t lane_mask = tile_mask >> (4 * h);
+      uint64_t tile_mask, lane_mask;
+      if constexpr (PQL) {
+        // the lane's 32 rows are 4 h + 8 j + i of each 32-row block: bit 8 j + i of the block's
+        // half of lane_mask (row_ok); tile_mask keeps its two wave-uniform meanings: 0 = no lane
+        // admits a row (tile skipped), all ones = every lane admits all of its rows
+        const u32x4* lb = (const u32x4*)(smem + LBL_OFF + cur * TILE_ROWS * 4);
+        uint32_t m[2] = {0u, 0u};
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const u32x4 v = lb[blk * 8 + 2 * j + h];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) m[blk] |= (uint32_t)(v[i] - f_lo <= f_span) << (8 * j + i);
+          }
+        lane_mask = (uint64_t)m[0] | ((uint64_t)m[1] << 32);
+        tile_mask = __all(lane_mask == 0x0f0f0f0f0f0f0f0full) ? ~0ull : (__any(lane_mask != 0ull) ? 1ull : 0ull);
+      } else {
+        const int lab = ((const int*)(smem + LBL_OFF + cur * TILE_ROWS * 4))[lane];
+        const bool lab_ok = (p.label_filter == MRAG_LABEL_ANY) ? (lab >= 0) : (lab == p.label_filter);
+        tile_mask = __ballot(lab_ok);
+        lane_mask = tile_mask >> (4 * h);
+      }
 
       if (wave_active && tile_mask != 0) {
         const char* tb = smem + cur * TILE_BYTES;
@@ -483,7 +527,16 @@ __device__ unsigned long long g_k7_stamps[K7_MAXWAVES * K7_NSTAMP];
 #define K7_STAMP(v)
 #endif
 
-template <int DP, int MODE = 0, int QB = 4>
+//
+// PQL (per-query labels): the tile tail masks per lane where the other instances mask per tile.
+// Lane (c16, g4) owns one query per query block and rows 16 rb + 4 g4 + r of the tile: at the tail
+// it reads those 16 labels from the tile's label buffer (four 16-byte LDS reads) and its QB
+// queries' (lo, span) pairs (kept in LDS beside the tile buffers: the QB = 4 instance has no
+// persistent register to spare, and at the tail the other accumulator buffer is dead), and sets
+// every accumulator whose row its query does not admit to -inf. That is before the group tests,
+// so another user's row never reaches the insertion path, and all three MODEs share it (both
+// record forms treat -inf as below everything). Padded query slots carry QLAB_NONE.
+template <int DP, int MODE = 0, int QB = 4, bool PQL = false>
 __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) {
   constexpr int KSTEPS = DP / 32;
   constexpr int ROW_BYTES = DP * 2;
@@ -496,7 +549,9 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
   constexpr int NGROUPS = 4 * QB;  // group g: query block g >> 2, row block g & 3
   constexpr int QPW3 = 16 * QB, QPG3 = SCAN2_WAVES * QPW3;  // queries per wave / workgroup
   constexpr int LBL_OFF = 2 * TILE_BYTES;
-  __shared__ __attribute__((aligned(16))) char smem[2 * TILE_BYTES + 2 * TILE_ROWS * 4];
+  constexpr int FLT_OFF = LBL_OFF + 2 * TILE_ROWS * 4;  // PQL: (lo, span) of the workgroup's queries
+  __shared__ __attribute__((aligned(16))) char smem[FLT_OFF + (PQL ? QPG3 * 8 : 0)];
+  using u32x2 = uint32_t __attribute__((ext_vector_type(2)));
 
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -518,6 +573,13 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
   }
   // query slot of block qb is slot0 + 16 qb; Qp is a multiple of QPG3 so every slot exists
   const int slot0 = qg * QPG3 + w * QPW3 + c16;
+  if constexpr (PQL) {
+    // thread t stores query t of the workgroup; read after the first tile's barrier at the earliest
+    if ((int)threadIdx.x < QPG3) {
+      const int32_t L = p.qlab[qg * QPG3 + (int)threadIdx.x];
+      ((u32x2*)(smem + FLT_OFF))[threadIdx.x] = u32x2{qlab_lo(L), qlab_span(L)};
+    }
+  }
 
   half8 qf[KSTEPS][QB];
 #pragma unroll
@@ -801,8 +863,8 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
             asm volatile("s_mov_b32 m0, %1" : "+v"(voff) : "s"(ldsw + pc * 1024));
           }
           static_assert(KLAB * FRONT >= GLDS_PER_WAVE, "label slots must follow the DMA k-steps");
-          if constexpr (kk == KLAB && j == 1) lab_v = ((const int*)(smem + LBL_OFF + X * TILE_ROWS * 4))[lane];
-          if constexpr (kk == KLAB + 1 && j == 1) tile_mask = __ballot((uint32_t)(lab_v - lab_lo) <= lab_span);
+          if constexpr (!PQL && kk == KLAB && j == 1) lab_v = ((const int*)(smem + LBL_OFF + X * TILE_ROWS * 4))[lane];
+          if constexpr (!PQL && kk == KLAB + 1 && j == 1) tile_mask = __ballot((uint32_t)(lab_v - lab_lo) <= lab_span);
         } else if constexpr ((j & 3) == 2) {  // ... and its DMA
           constexpr int pc = FRONT * kk + (j >> 2);
           if constexpr ((j >> 2) < FRONT && pc < GLDS_PER_WAVE) {
@@ -822,13 +884,35 @@ __global__ __launch_bounds__(SCAN2_THREADS) void knn_scan3_kernel(ScanParams p) 
       });
     });
     end_of_tile(false);
-    if constexpr (QB == 1) {
+    if constexpr (PQL) {
+      // per-lane mask (see the kernel's comment); buffer X's labels are not rewritten before the barrier
+      const u32x4* lb = (const u32x4*)(smem + LBL_OFF + X * TILE_ROWS * 4);
+      u32x4 labs[4];
+      u32x2 flt[QB];
+#pragma unroll
+      for (int rb = 0; rb < 4; ++rb) labs[rb] = lb[4 * rb + g4];
+#pragma unroll
+      for (int qb = 0; qb < QB; ++qb) flt[qb] = ((const u32x2*)(smem + FLT_OFF))[w * QPW3 + 16 * qb + c16];
+      mfma16_guard(acc[X]);
+#pragma unroll
+      for (int rb = 0; rb < 4; ++rb) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int qb = 0; qb < QB; ++qb)
+            acc[X][rb][qb][r] = labs[rb][r] - flt[qb][0] <= flt[qb][1] ? acc[X][rb][qb][r] : -INFINITY;
+        // one row block's selects done here: left to itself the compiler computes all 64 compares
+        // first and sinks the selects to the next tile's group tests, which spills
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) asm volatile("" : "+v"(acc[X][rb][qb]));
+      }
+    } else if constexpr (QB == 1) {
       // K7s: the tile's labels, read after its MFMAs (a read at the top would wait for its LDS
       // round trip before the first MFMA; buffer X is not rewritten before the barrier)
       lab_v = ((const int*)(smem + LBL_OFF + X * TILE_ROWS * 4))[lane];
       tile_mask = __ballot((uint32_t)(lab_v - lab_lo) <= lab_span);
     }
-    if (tile_mask != ~0ull) {
+    if (!PQL && tile_mask != ~0ull) {
       mfma16_guard(acc[X]);
       const uint64_t lm = tile_mask >> (4 * g4);
 #pragma unroll
@@ -1024,9 +1108,11 @@ struct ResolveParams {
   float* part_s;
   int32_t* part_i;
   float* part_tau;
+  const int32_t* qlab;  // PQL: the query's own filter, [Qp] (ScanParams::qlab)
 };
 constexpr int XCAP = XLISTS * 8;
 
+template <bool PQL = false>
 __global__ __launch_bounds__(64) void sample_resolve_kernel(ResolveParams p) {
   using u32x4 = uint32_t __attribute__((ext_vector_type(4)));
   constexpr int PER_LANE = 32;  // splits <= 256: lane l holds splits l, l + 64, ...: 4 x 4 lane groups x {m1, m2}
@@ -1089,8 +1175,13 @@ __global__ __launch_bounds__(64) void sample_resolve_kernel(ResolveParams p) {
   }
   __syncthreads();
 
-  const int lab_lo = p.label_filter == MRAG_LABEL_ANY ? 0 : p.label_filter;
-  const uint32_t lab_span = p.label_filter == MRAG_LABEL_ANY ? 0x7fffffffu : 0u;
+  int lab_lo = p.label_filter == MRAG_LABEL_ANY ? 0 : p.label_filter;
+  uint32_t lab_span = p.label_filter == MRAG_LABEL_ANY ? 0x7fffffffu : 0u;
+  if constexpr (PQL) {
+    const int32_t L = p.qlab[q];
+    lab_lo = (int)qlab_lo(L);
+    lab_span = qlab_span(L);
+  }
   const int gsel = lane >> 4, rr = (lane >> 2) & 3, sub = lane & 3;
   const half8* qrow = (const half8*)(p.q16 + (size_t)q * p.DP);
   int cnt = 0;
@@ -1110,7 +1201,7 @@ __global__ __launch_bounds__(64) void sample_resolve_kernel(ResolveParams p) {
     acc += __shfl_xor(acc, 1);
     acc += __shfl_xor(acc, 2);
     const int lab = p.labels[row];
-    const bool take = have && sub == 0 && (uint32_t)(lab - lab_lo) <= lab_span && acc > theta_f;
+    const bool take = have && sub == 0 && (uint32_t)lab - (uint32_t)lab_lo <= lab_span && acc > theta_f;
     const uint64_t b = __ballot(take);
     if (take) {
       const int pos = cnt + __popcll(b & lt);
@@ -1785,32 +1876,63 @@ scan_fn pick_scan(int KL, bool collect) {
                    : (KL <= 16 ? knn_scan_kernel<DP, 16, false> : knn_scan_kernel<DP, 32, false>);
   }
 }
+// The per-query-label instances of v1: K7c at every width, and the top-k scan at the one depth
+// kl_for() gives a width for k > 64 (the only k the plan sends to v1) up to PQL_V1_MAX_DP: the
+// wider ones do not fit their registers, and the plan sends those searches to K7g.
+template <int DP>
+scan_fn pick_scan_pql(int KL, bool collect) {
+  if (collect) return knn_scan_kernel<DP, 8, true, true>;
+  if constexpr (DP <= PQL_V1_MAX_DP) {
+    constexpr int KLD = DP >= 256 ? 16 : 32;
+    return KL == KLD ? knn_scan_kernel<DP, KLD, false, true> : nullptr;
+  } else {
+    return nullptr;
+  }
+}
 
-template <int MODE, int QB>
+template <int MODE, int QB, bool PQL>
 scan_fn get_scan3m(int DP) {
   switch (DP) {
-    case 128: return knn_scan3_kernel<128, MODE, QB>;
-    case 256: return knn_scan3_kernel<256, MODE, QB>;
-    case 384: return knn_scan3_kernel<384, MODE, QB>;
-    case 512: return knn_scan3_kernel<512, MODE, QB>;
+    case 128: return knn_scan3_kernel<128, MODE, QB, PQL>;
+    case 256: return knn_scan3_kernel<256, MODE, QB, PQL>;
+    case 384: return knn_scan3_kernel<384, MODE, QB, PQL>;
+    case 512: return knn_scan3_kernel<512, MODE, QB, PQL>;
     default: return nullptr;
   }
 }
 // the sample passes (MODE 1: seed only; MODE 2: counting) exist for the 256-query groups only (K7s
-// runs without them)
-scan_fn get_scan3(int DP, int mode, int qb) {
-  if (qb == 1) return mode ? nullptr : get_scan3m<0, 1>(DP);
-  return mode == 2 ? get_scan3m<2, 4>(DP) : mode == 1 ? get_scan3m<1, 4>(DP) : get_scan3m<0, 4>(DP);
+// runs without them); pql: the per-query-label instances
+scan_fn get_scan3(int DP, int mode, int qb, bool pql) {
+  if (pql) {
+    if (qb == 1) return mode ? nullptr : get_scan3m<0, 1, true>(DP);
+    return mode == 2 ? get_scan3m<2, 4, true>(DP) : mode == 1 ? get_scan3m<1, 4, true>(DP) : get_scan3m<0, 4, true>(DP);
+  }
+  if (qb == 1) return mode ? nullptr : get_scan3m<0, 1, false>(DP);
+  return mode == 2 ? get_scan3m<2, 4, false>(DP) : mode == 1 ? get_scan3m<1, 4, false>(DP) : get_scan3m<0, 4, false>(DP);
 }
 
-scan_fn get_scan(int DP, int KL, bool collect) {
+scan_fn get_scan(int DP, int KL, bool collect, bool pql) {
   switch (DP) {
-    case 128: return pick_scan<128>(KL, collect);
-    case 256: return pick_scan<256>(KL, collect);
-    case 384: return pick_scan<384>(KL, collect);
-    case 512: return pick_scan<512>(KL, collect);
+    case 128: return pql ? pick_scan_pql<128>(KL, collect) : pick_scan<128>(KL, collect);
+    case 256: return pql ? pick_scan_pql<256>(KL, collect) : pick_scan<256>(KL, collect);
+    case 384: return pql ? pick_scan_pql<384>(KL, collect) : pick_scan<384>(KL, collect);
+    case 512: return pql ? pick_scan_pql<512>(KL, collect) : pick_scan<512>(KL, collect);
     default: return nullptr;
   }
+}
+
+// Per-query filters of a labelled search -> the context's [Qp] array the PQL kernels read: entry
+// i < nq as given (anything below MRAG_LABEL_ANY becomes QLAB_NONE: it matches nothing), the
+// padded query slots QLAB_NONE.
+__global__ void qlab_prep_kernel(const int32_t* __restrict__ in, int64_t nq, int64_t Qp, int32_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Qp) return;
+  int32_t L = QLAB_NONE;
+  if (i < nq) {
+    L = in[i];
+    if (L < MRAG_LABEL_ANY) L = QLAB_NONE;
+  }
+  out[i] = L;
 }
 
 }  // namespace
@@ -1823,6 +1945,7 @@ scan_fn get_scan(int DP, int KL, bool collect) {
 struct SearchCtx {
   DevBuf qin, q32, qn, q16, part_s, part_i, thresh, fail_list, counters, cand_cnt, cand, scratch;
   DevBuf out_s, out_s64, out_r, theta, part_tau, rec;
+  DevBuf qlab_in, qlab;  // labelled search: the filters as given (host arrays land here) / per query slot
   int32_t* host_counters = nullptr;  // pinned [2]: fail_cnt, overflow
   int32_t* host_fail = nullptr;      // coherent pinned [4]: [0] = some query failed K8's certificate
   hipEvent_t done = nullptr;         // end of the search's device work (waited by spinning)
@@ -1961,6 +2084,7 @@ struct Search {
   bool host;  // queries and outputs are host pointers
   int64_t nq;
   int k, label_filter;
+  const int32_t* label_filters;  // per query, [nq] (host or device like queries), or null: label_filter for all
   int64_t row_offset;
   float* os;
   double* os64;  // may be null
@@ -2007,6 +2131,18 @@ int stage_queries(const Search& q, const SearchPlan& p) {
   if (int rc = ensure(c->q32, (size_t)p.Qp * DP * 4)) return rc;
   if (int rc = ensure(c->qn, (size_t)p.Qp * 8)) return rc;
   if (int rc = ensure(c->q16, (size_t)p.Qp * DP * 2)) return rc;
+  if (q.label_filters) {
+    const int32_t* lsrc = q.label_filters;
+    if (q.host) {
+      if (int rc = ensure(c->qlab_in, (size_t)q.nq * 4)) return rc;
+      MRAG_HIP(hipMemcpyAsync(c->qlab_in.p, q.label_filters, (size_t)q.nq * 4, hipMemcpyHostToDevice, q.s));
+      lsrc = (const int32_t*)c->qlab_in.p;
+    }
+    if (int rc = ensure(c->qlab, (size_t)p.Qp * 4)) return rc;
+    hipLaunchKernelGGL(qlab_prep_kernel, dim3((unsigned)((p.Qp + 255) / 256)), dim3(256), 0, q.s, lsrc, q.nq,
+                       (int64_t)p.Qp, (int32_t*)c->qlab.p);
+    MRAG_CHECK_LAUNCH();
+  }
   PrepClear clr{};
   if (p.path != SearchPath::Generic) {
     if (int rc = size_buffers(c, p)) return rc;
@@ -2042,6 +2178,7 @@ ScanParams scan_params(const Search& q, const SearchPlan& p) {
   sp.rec = p.counting ? (uint32_t*)c->rec.p : nullptr;
   sp.rec_keep = p.rec_keep;
   sp.skip_magic = p.skip_magic;
+  sp.qlab = p.pql ? (const int32_t*)c->qlab.p : nullptr;
   return sp;
 }
 
@@ -2062,6 +2199,7 @@ ResolveParams resolve_params(const Search& q, const SearchPlan& p, const ScanPar
   rp.part_s = sp.part_s;
   rp.part_i = sp.part_i;
   rp.part_tau = sp.part_tau;
+  rp.qlab = sp.qlab;
   return rp;
 }
 
@@ -2141,6 +2279,7 @@ mrag_knn::GenericSearch generic_args(const Search& q) {
   ga.nq = (int)q.nq;
   ga.k = q.k;
   ga.label_filter = q.label_filter;
+  ga.label_filters = q.label_filters ? (const int32_t*)c->qlab.p : nullptr;
   ga.row_offset = q.row_offset;
   ga.out_s = q.os;
   ga.out_s64 = q.os64;
@@ -2153,10 +2292,11 @@ mrag_knn::GenericSearch generic_args(const Search& q) {
 int sample_stage(const Search& q, const SearchPlan& p, ScanParams sp) {
   sp.skip_magic = 0;
   const dim3 sgrid((unsigned)(p.qgroups * p.S));
-  hipLaunchKernelGGL(get_scan3(q.ix->DP, p.counting ? 2 : 1, p.qb), sgrid, dim3(SCAN2_THREADS), 0, q.s, sp);
+  hipLaunchKernelGGL(get_scan3(q.ix->DP, p.counting ? 2 : 1, p.qb, p.pql), sgrid, dim3(SCAN2_THREADS), 0, q.s, sp);
   MRAG_CHECK_LAUNCH();
   if (p.counting)
-    hipLaunchKernelGGL(sample_resolve_kernel, dim3((unsigned)q.nq), dim3(64), 0, q.s, resolve_params(q, p, sp));
+    hipLaunchKernelGGL(p.pql ? sample_resolve_kernel<true> : sample_resolve_kernel<false>, dim3((unsigned)q.nq),
+                       dim3(64), 0, q.s, resolve_params(q, p, sp));
   else
     hipLaunchKernelGGL(theta_init_kernel, dim3((unsigned)q.nq), dim3(64), 0, q.s, (const float*)sp.part_s, 4 * p.S,
                        (int)p.Qp, q.k, sp.theta);
@@ -2237,8 +2377,8 @@ int collect_stage(const Search& q, const SearchPlan& p, ScanParams sp, scan_fn c
 // The fused search (v3 or v1 scan, K8, collect when needed) along its plan.
 int search_fused(const Search& q, const SearchPlan& p, SearchStats& st) {
   const int DP = q.ix->DP;
-  const scan_fn scan = p.path == SearchPath::V3 ? get_scan3(DP, 0, p.qb) : get_scan(DP, p.KL, false);
-  const scan_fn collect = get_scan(DP, 8, true);
+  const scan_fn scan = p.path == SearchPath::V3 ? get_scan3(DP, 0, p.qb, p.pql) : get_scan(DP, p.KL, false, p.pql);
+  const scan_fn collect = get_scan(DP, 8, true, p.pql);
   if (!scan || !collect) return mrag::fail(MRAG_ERR_UNSUPPORTED, "no scan kernel for DP=%d", DP);
   st.info[0] = p.S;
   st.info[1] = (int32_t)p.Qp;
@@ -2249,6 +2389,78 @@ int search_fused(const Search& q, const SearchPlan& p, SearchStats& st) {
     if (int rc = sample_stage(q, p, sp)) return rc;
   if (int rc = scan_merge_stage(q, p, sp, scan, &st.uncertified)) return rc;
   if (st.uncertified > 0) return collect_stage(q, p, sp, collect, st);
+  return MRAG_OK;
+}
+
+// mrag_knn_search (label_filters null: label_filter for every query) and mrag_knn_search_labels.
+int search_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k, int32_t label_filter,
+                 const int32_t* label_filters, int64_t row_offset, float* out_scores, double* out_scores64,
+                 int64_t* out_rows, int32_t ptr_kind, void* stream_arg) {
+  std::shared_lock<std::shared_mutex> rl(ix->rw);
+  mrag::DeviceGuard g(ix->device);
+  if (nq == 0) return MRAG_OK;
+  SearchCtx* c = nullptr;
+  if (int rc = ctx_get(ix, &c)) return rc;
+  CtxLease lease{ix, c};
+  bool profile;
+  {
+    std::lock_guard<std::mutex> lk(ix->pool_mu);
+    profile = ix->profile;
+  }
+  MRAG_REQUIRE(queries && out_scores && out_rows, "NULL query/output pointer");
+  hipStream_t s = stream_arg ? (hipStream_t)stream_arg : ix->stream;
+  const bool host = ptr_kind == MRAG_PTR_HOST;
+  if (!host && !stream_arg)
+    if (int rc = mrag::wait_null_stream(c->null_ev, s)) return rc;
+  // destroyed before the lease and the shared lock: an error after the first launch drains s
+  // before the context returns to the pool and mutations may free the corpus buffers
+  mrag::StreamDrain drain(s);
+  const int64_t nout = nq * k;
+
+  // output destinations (device)
+  float* os = out_scores;
+  double* os64 = out_scores64;
+  int64_t* orr = out_rows;
+  if (host) {
+    if (int rc = ensure(c->out_s, nout * 4)) return rc;
+    if (int rc = ensure(c->out_r, nout * 8)) return rc;
+    os = (float*)c->out_s.p;
+    orr = (int64_t*)c->out_r.p;
+    if (out_scores64) {
+      if (int rc = ensure(c->out_s64, nout * 8)) return rc;
+      os64 = (double*)c->out_s64.p;
+    }
+  }
+
+  const Search q{ix, c, s, queries, host, nq, k, label_filter, label_filters, row_offset, os, os64, orr, profile};
+  const SearchPlan plan = plan_search(ix->n, nq, k, ix->DP, label_filters != nullptr);
+  SearchStats st;
+  switch (plan.path) {
+    case SearchPath::Empty:
+      hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, os, os64, orr,
+                         nout);
+      MRAG_CHECK_LAUNCH();
+      break;
+    case SearchPath::Generic:
+      if (int rc = stage_queries(q, plan)) return rc;
+      if (int rc = mrag_knn::search_generic(generic_args(q), c->gws, s, nullptr)) return rc;
+      break;
+    default:
+      if (int rc = search_fused(q, plan, st)) return rc;
+  }
+
+  if (host) {
+    MRAG_HIP(hipMemcpyAsync(out_scores, os, nout * 4, hipMemcpyDeviceToHost, s));
+    MRAG_HIP(hipMemcpyAsync(out_rows, orr, nout * 8, hipMemcpyDeviceToHost, s));
+    if (out_scores64) MRAG_HIP(hipMemcpyAsync(out_scores64, os64, nout * 8, hipMemcpyDeviceToHost, s));
+  }
+  if (int rc = wait_stream(c, s)) return rc;
+  drain.armed = false;
+  std::lock_guard<std::mutex> lk(ix->pool_mu);
+  ix->last_uncertified = st.uncertified;
+  ix->last_retries = st.retries;
+  ix->last_ctx = c;
+  std::copy(st.info, st.info + 8, ix->last_info);
   return MRAG_OK;
 }
 
@@ -2401,72 +2613,27 @@ int mrag_knn_search(mrag_knn_index* ix, const float* queries, int64_t nq, int32_
   MRAG_REQUIRE(label_filter >= MRAG_LABEL_ANY, "label filter %d invalid", label_filter);
   MRAG_REQUIRE(ptr_kind == MRAG_PTR_HOST || ptr_kind == MRAG_PTR_DEVICE, "bad ptr_kind %d", ptr_kind);
   MRAG_REQUIRE(nq < (1 << 24), "too many queries in one call");
-  std::shared_lock<std::shared_mutex> rl(ix->rw);
-  mrag::DeviceGuard g(ix->device);
-  if (nq == 0) return MRAG_OK;
-  SearchCtx* c = nullptr;
-  if (int rc = ctx_get(ix, &c)) return rc;
-  CtxLease lease{ix, c};
-  bool profile;
-  {
-    std::lock_guard<std::mutex> lk(ix->pool_mu);
-    profile = ix->profile;
-  }
-  MRAG_REQUIRE(queries && out_scores && out_rows, "NULL query/output pointer");
-  hipStream_t s = stream_arg ? (hipStream_t)stream_arg : ix->stream;
-  const bool host = ptr_kind == MRAG_PTR_HOST;
-  if (!host && !stream_arg)
-    if (int rc = mrag::wait_null_stream(c->null_ev, s)) return rc;
-  // destroyed before the lease and the shared lock: an error after the first launch drains s
-  // before the context returns to the pool and mutations may free the corpus buffers
-  mrag::StreamDrain drain(s);
-  const int64_t nout = nq * k;
+  return search_entry(ix, queries, nq, k, label_filter, nullptr, row_offset, out_scores, out_scores64, out_rows,
+                      ptr_kind, stream_arg);
+}
 
-  // output destinations (device)
-  float* os = out_scores;
-  double* os64 = out_scores64;
-  int64_t* orr = out_rows;
-  if (host) {
-    if (int rc = ensure(c->out_s, nout * 4)) return rc;
-    if (int rc = ensure(c->out_r, nout * 8)) return rc;
-    os = (float*)c->out_s.p;
-    orr = (int64_t*)c->out_r.p;
-    if (out_scores64) {
-      if (int rc = ensure(c->out_s64, nout * 8)) return rc;
-      os64 = (double*)c->out_s64.p;
-    }
-  }
-
-  const Search q{ix, c, s, queries, host, nq, k, label_filter, row_offset, os, os64, orr, profile};
-  const SearchPlan plan = plan_search(ix->n, nq, k, ix->DP);
-  SearchStats st;
-  switch (plan.path) {
-    case SearchPath::Empty:
-      hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, os, os64, orr,
-                         nout);
-      MRAG_CHECK_LAUNCH();
-      break;
-    case SearchPath::Generic:
-      if (int rc = stage_queries(q, plan)) return rc;
-      if (int rc = mrag_knn::search_generic(generic_args(q), c->gws, s, nullptr)) return rc;
-      break;
-    default:
-      if (int rc = search_fused(q, plan, st)) return rc;
-  }
-
-  if (host) {
-    MRAG_HIP(hipMemcpyAsync(out_scores, os, nout * 4, hipMemcpyDeviceToHost, s));
-    MRAG_HIP(hipMemcpyAsync(out_rows, orr, nout * 8, hipMemcpyDeviceToHost, s));
-    if (out_scores64) MRAG_HIP(hipMemcpyAsync(out_scores64, os64, nout * 8, hipMemcpyDeviceToHost, s));
-  }
-  if (int rc = wait_stream(c, s)) return rc;
-  drain.armed = false;
-  std::lock_guard<std::mutex> lk(ix->pool_mu);
-  ix->last_uncertified = st.uncertified;
-  ix->last_retries = st.retries;
-  ix->last_ctx = c;
-  std::copy(st.info, st.info + 8, ix->last_info);
-  return MRAG_OK;
+int mrag_knn_search_labels(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k,
+                           const int32_t* label_filters, int64_t row_offset, float* out_scores,
+                           double* out_scores64, int64_t* out_rows, int32_t ptr_kind, void* stream_arg) {
+  MRAG_REQUIRE(ix != nullptr, "NULL index");
+  MRAG_REQUIRE(nq >= 0, "negative query count");
+  MRAG_REQUIRE(k >= 1 && k <= mrag_knn::GENERIC_MAX_K, "k=%d unsupported (1..%d)", k, mrag_knn::GENERIC_MAX_K);
+  MRAG_REQUIRE(ptr_kind == MRAG_PTR_HOST || ptr_kind == MRAG_PTR_DEVICE, "bad ptr_kind %d", ptr_kind);
+  MRAG_REQUIRE(nq < (1 << 24), "too many queries in one call");
+  MRAG_REQUIRE(nq == 0 || label_filters != nullptr, "NULL label filters");
+  // a host array is checked here, before any launch; a device array's entries below
+  // MRAG_LABEL_ANY match nothing (mrag.h)
+  if (ptr_kind == MRAG_PTR_HOST)
+    for (int64_t i = 0; i < nq; ++i)
+      MRAG_REQUIRE(label_filters[i] >= MRAG_LABEL_ANY, "label filter %d of query %lld invalid", label_filters[i],
+                   (long long)i);
+  return search_entry(ix, queries, nq, k, MRAG_LABEL_ANY, label_filters, row_offset, out_scores, out_scores64,
+                      out_rows, ptr_kind, stream_arg);
 }
 
 #ifdef MRAG_K7_STAMPS

@@ -32,6 +32,7 @@ struct GenericSearch {
   int nq;
   int k;
   int32_t label_filter;
+  const int32_t* label_filters;  // per query [nq] (device), or null: label_filter for every query
   int64_t row_offset;
   // outputs (device) [nq][k]
   float* out_s;

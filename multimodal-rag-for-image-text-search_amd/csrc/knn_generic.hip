@@ -45,14 +45,18 @@ __device__ __forceinline__ bool label_ok(int32_t lab, int32_t filter) {
   return filter == MRAG_LABEL_ANY ? lab >= 0 : lab == filter;
 }
 
-// One workgroup = one query row of S x one slice of the chunk's columns.
+// One workgroup = one query row of S x one slice of the chunk's columns. PQL: the query's own
+// filter, qfilter[query], in place of the search's one.
+template <bool PQL = false>
 __global__ __launch_bounds__(256) void score_hist_kernel(const float* __restrict__ S, int ncols,
                                                          const int32_t* __restrict__ labels, int32_t filter,
-                                                         uint32_t* __restrict__ hist) {
+                                                         uint32_t* __restrict__ hist,
+                                                         const int32_t* __restrict__ qfilter) {
   __shared__ uint32_t h[HIST_BINS];
   for (int i = threadIdx.x; i < HIST_BINS; i += 256) h[i] = 0;
   __syncthreads();
   const int qi = blockIdx.x;
+  if constexpr (PQL) filter = qfilter[qi];
   const float* srow = S + (size_t)qi * ncols;
   const int per = ((ncols + gridDim.y - 1) / gridDim.y + 3) & ~3;
   const int c0 = blockIdx.y * per, c1 = min(ncols, c0 + per);
@@ -126,12 +130,15 @@ __global__ __launch_bounds__(64) void hist_threshold_kernel(const uint32_t* __re
   }
 }
 
+template <bool PQL = false>
 __global__ __launch_bounds__(256) void score_collect_kernel(const float* __restrict__ S, int ncols, int64_t row0,
                                                             const int32_t* __restrict__ labels, int32_t filter,
                                                             const float* __restrict__ thr,
                                                             const int64_t* __restrict__ off,
-                                                            int32_t* __restrict__ cnt, int32_t* __restrict__ cand) {
+                                                            int32_t* __restrict__ cnt, int32_t* __restrict__ cand,
+                                                            const int32_t* __restrict__ qfilter) {
   const int qi = blockIdx.x;
+  if constexpr (PQL) filter = qfilter[qi];
   const float t = thr[qi];
   const float* srow = S + (size_t)qi * ncols;
   const int per = ((ncols + gridDim.y - 1) / gridDim.y + 3) & ~3;
@@ -363,8 +370,9 @@ int search_generic(const GenericSearch& a, Workspace (&ws)[8], hipStream_t s, in
     for (int64_t r0 = 0; r0 < ncols_total; r0 += ch) {
       const int nc = (int)std::min<int64_t>(ch, ncols_total - r0);
       if (int rc = gemm_scores(a, qb, mq, r0, nc, S, s)) return rc;
-      hipLaunchKernelGGL(score_hist_kernel, dim3((unsigned)mq, (unsigned)ysplit), dim3(256), 0, s, S, nc,
-                         a.labels + r0, a.label_filter, hist);
+      hipLaunchKernelGGL(a.label_filters ? score_hist_kernel<true> : score_hist_kernel<false>,
+                         dim3((unsigned)mq, (unsigned)ysplit), dim3(256), 0, s, S, nc, a.labels + r0, a.label_filter,
+                         hist, a.label_filters ? a.label_filters + qb : nullptr);
       MRAG_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(hist_threshold_kernel, dim3((unsigned)mq), dim3(64), 0, s, hist, a.k, eps2w, thr, bound);
@@ -393,8 +401,10 @@ int search_generic(const GenericSearch& a, Workspace (&ws)[8], hipStream_t s, in
         const int nc = (int)std::min<int64_t>(ch2, ncols_total - r0);
         if (int rc = gemm_scores(a, qb + lo, m, r0, nc, S, s)) return rc;
         const int ys = std::max(1, std::min<int>(nc / 4096, 64));
-        hipLaunchKernelGGL(score_collect_kernel, dim3((unsigned)m, (unsigned)ys), dim3(256), 0, s, S, nc, r0,
-                           a.labels + r0, a.label_filter, thr + lo, off, cnt, (int32_t*)ws[6].p);
+        hipLaunchKernelGGL(a.label_filters ? score_collect_kernel<true> : score_collect_kernel<false>,
+                           dim3((unsigned)m, (unsigned)ys), dim3(256), 0, s, S, nc, r0, a.labels + r0,
+                           a.label_filter, thr + lo, off, cnt, (int32_t*)ws[6].p,
+                           a.label_filters ? a.label_filters + qb + lo : nullptr);
         MRAG_CHECK_LAUNCH();
       }
       FinalParams fp{};

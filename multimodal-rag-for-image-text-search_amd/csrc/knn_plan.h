@@ -18,6 +18,7 @@ constexpr int QPG = 8 * QPW;             // v1 / K7c: queries per workgroup (8 w
 constexpr int MAX_MERGE_ENTRIES = 4096;  // splits * KL cap (LDS sort in K8)
 constexpr int MAX_K = 256;               // deepest k of the fused scan (K7g above)
 constexpr int MAX_DP = 512;              // widest padded row of the fused scan (K7g above)
+constexpr int PQL_V1_MAX_DP = 256;       // per-query labels: widest row of v1's top-k scan (K7g above)
 #ifndef MRAG_SAMPLE_STRIDE
 #define MRAG_SAMPLE_STRIDE 16
 #endif
@@ -58,6 +59,10 @@ struct SearchPlan {
   int Mp;            // M rounded up to a power of two
   int sel;           // key selection: register top-64 (1) / top-128 (2) fold, or 0 = bitonic sort
   size_t merge_lds;  // dynamic LDS bytes of the K8 launch
+  // per-query labels (mrag_knn_search_labels): the scan, sample, resolve, K7c and K7g kernels run
+  // as their PQL instances, which mask rows per query; every other field is what the unlabelled
+  // search of the same shape gets
+  bool pql;
 };
 
 inline int64_t next_pow2(int64_t x) {
@@ -89,14 +94,21 @@ inline int sample_stride_for(int k) { return k > 16 ? 4 : SAMPLE_STRIDE; }
 // over all tiles (the rows above its seed, about k x stride, would not fit the extra lists).
 inline bool counting_sample_for(int k) { return k <= 16; }
 
-// The plan of a search of nq >= 1 queries for the k best of n rows of padded width DP.
-inline SearchPlan plan_search(int64_t n, int64_t nq, int k, int DP) {
+// The plan of a search of nq >= 1 queries for the k best of n rows of padded width DP;
+// per_query_labels: every query carries its own label filter. The PQL instances of the v3 scan
+// (every DP, QB and MODE), of the resolve kernel and of K7c build without scratch (DESIGN.md §4
+// "Kernel resources"), so a labelled search keeps the geometry, the sample pass and K8's sizes of
+// the unlabelled one. The one exception is v1's top-k scan (k > 64) at DP = 384 and 512: with the
+// lane's filter next to its lists and query fragments it needs 60 / 68 bytes of scratch per lane,
+// so labelled searches of those shapes take K7g, which filters per query at no register cost.
+inline SearchPlan plan_search(int64_t n, int64_t nq, int k, int DP, bool per_query_labels = false) {
   SearchPlan p{};
+  p.pql = per_query_labels;
   if (n == 0) {
     p.path = SearchPath::Empty;
     return p;
   }
-  if (DP > MAX_DP || k > MAX_K) {
+  if (DP > MAX_DP || k > MAX_K || (per_query_labels && k > 64 && DP > PQL_V1_MAX_DP)) {
     p.path = SearchPath::Generic;
     p.Qp = nq;  // K7g pads nothing
     return p;

@@ -25,12 +25,16 @@ const char* const CONDITIONS[] = {
     "sampled implies v3, qb == 4 and sample_tiles >= 4",
     "counting implies sampled, idbits <= REC_ID_BITS_MAX, 4 max_sample_tiles <= 2^idbits, stride > 1",
     "K8's LDS bytes <= 65536 (the launch sets no larger limit)",
+    "per-query labels: K7g where v1's top-k scan has no such instance (k > 64, DP > PQL_V1_MAX_DP), pql set",
 };
 
-// 0, or the index in CONDITIONS of the first condition the plan of (n, nq, k, dim) violates.
-int violation(int64_t n, int64_t nq, int k, int dim) {
+// 0, or the index in CONDITIONS of the first condition the plan of (n, nq, k, dim) violates
+// (labelled: the plan of a search with per-query labels).
+int violation(int64_t n, int64_t nq, int k, int dim, bool labelled = false) {
   const int DP = (dim + 127) / 128 * 128;
-  const SearchPlan p = plan_search(n, nq, k, DP);
+  const SearchPlan p = labelled ? plan_search(n, nq, k, DP, true) : plan_search(n, nq, k, DP);
+  if (p.pql != labelled) return 9;
+  if (labelled && k > 64 && DP > PQL_V1_MAX_DP) return p.path == SearchPath::Generic && p.Qp == nq ? 0 : 9;
   const bool v3 = p.path == SearchPath::V3;
   if (!(v3 || p.path == SearchPath::V1) || v3 != (k <= 64)) return 1;
   if (!(1 <= p.S && p.S <= p.ntiles && p.S * p.KL <= MAX_MERGE_ENTRIES && (p.S < 8 || p.S % 8 == 0))) return 2;
@@ -47,6 +51,46 @@ int violation(int64_t n, int64_t nq, int k, int dim) {
   return 0;
 }
 
+void plan_fields(const SearchPlan& p, int64_t* out) {
+  const int64_t f[] = {(int64_t)p.path, p.qb,      p.qpg,          p.Qp,
+                       p.qgroups,       p.ntiles,  p.KL,           p.S,
+                       p.stride,        p.sampled, p.sample_tiles, p.max_sample_tiles,
+                       p.idbits,        p.counting, p.SX,          p.rec_keep,
+                       p.skip_magic,    p.M,       p.R,            p.Mp,
+                       p.sel,           (int64_t)p.merge_lds};
+  for (int i = 0; i < (int)(sizeof(f) / sizeof(f[0])); ++i) out[i] = f[i];
+}
+
+// knn_plan_sweep's grid over the plans of unlabelled or labelled searches.
+int64_t sweep(bool labelled, int64_t* out) {
+  const int64_t ns[] = {1,      63,     64,      65,      4095,    4096,    5000,   100000,
+                        262143, 262144, 270000, 1 << 20, 1 << 24, 1 << 26, 1 << 30};
+  const int64_t nqs[] = {1, 31, 32, 33, 64, 65, 255, 256, 257, 1000, 4096, 65536, (1 << 24) - 1};
+  const int ks[] = {1, 8, 9, 16, 17, 32, 33, 64, 65, 100, 256};
+  const int dims[] = {1, 100, 128, 129, 256, 384, 512};
+  int64_t points = 0, bad = 0, max_lds = 0;
+  for (int64_t n : ns)
+    for (int64_t nq : nqs)
+      for (int k : ks)
+        for (int dim : dims) {
+          ++points;
+          const int DP = (dim + 127) / 128 * 128;
+          const SearchPlan p = labelled ? plan_search(n, nq, k, DP, true) : plan_search(n, nq, k, DP);
+          max_lds = std::max<int64_t>(max_lds, (int64_t)p.merge_lds);
+          const int v = violation(n, nq, k, dim, labelled);
+          if (v && bad++ == 0) {
+            out[2] = n;
+            out[3] = nq;
+            out[4] = k;
+            out[5] = dim;
+            out[6] = v;
+          }
+        }
+  out[0] = points;
+  out[1] = max_lds;
+  return bad;
+}
+
 }  // namespace
 
 extern "C" {
@@ -58,14 +102,15 @@ const char* knn_plan_field_names() {
 
 // The plan of (n, nq, k, DP), in the order of knn_plan_field_names(); path as in SearchPath.
 void knn_plan_fields(int64_t n, int64_t nq, int k, int DP, int64_t* out) {
-  const SearchPlan p = plan_search(n, nq, k, DP);
-  const int64_t f[] = {(int64_t)p.path, p.qb,      p.qpg,          p.Qp,
-                       p.qgroups,       p.ntiles,  p.KL,           p.S,
-                       p.stride,        p.sampled, p.sample_tiles, p.max_sample_tiles,
-                       p.idbits,        p.counting, p.SX,          p.rec_keep,
-                       p.skip_magic,    p.M,       p.R,            p.Mp,
-                       p.sel,           (int64_t)p.merge_lds};
-  for (int i = 0; i < (int)(sizeof(f) / sizeof(f[0])); ++i) out[i] = f[i];
+  plan_fields(plan_search(n, nq, k, DP), out);
+}
+
+// The plan with plan_search's last argument given: the fields of knn_plan_field_names(), then
+// SearchPlan::pql (per_query_labels != 0: a search with one label filter per query).
+void knn_plan_fields_labels(int64_t n, int64_t nq, int k, int DP, int per_query_labels, int64_t* out) {
+  const SearchPlan p = plan_search(n, nq, k, DP, per_query_labels != 0);
+  plan_fields(p, out);
+  out[22] = p.pql;
 }
 
 // The collect stage's plan for `uncertified` failing queries of that search: cgroups, Sc, ccap.
@@ -80,32 +125,10 @@ const char* knn_plan_condition(int i) { return CONDITIONS[i]; }
 
 // Checks every point of the grid; returns the number of violating points. out[0] = points,
 // out[1] = largest K8 LDS figure, out[2..6] = n, nq, k, dim and condition of the first violation.
-int64_t knn_plan_sweep(int64_t* out) {
-  const int64_t ns[] = {1,      63,     64,      65,      4095,    4096,    5000,   100000,
-                        262143, 262144, 270000, 1 << 20, 1 << 24, 1 << 26, 1 << 30};
-  const int64_t nqs[] = {1, 31, 32, 33, 64, 65, 255, 256, 257, 1000, 4096, 65536, (1 << 24) - 1};
-  const int ks[] = {1, 8, 9, 16, 17, 32, 33, 64, 65, 100, 256};
-  const int dims[] = {1, 100, 128, 129, 256, 384, 512};
-  int64_t points = 0, bad = 0, max_lds = 0;
-  for (int64_t n : ns)
-    for (int64_t nq : nqs)
-      for (int k : ks)
-        for (int dim : dims) {
-          ++points;
-          max_lds = std::max<int64_t>(max_lds, (int64_t)plan_search(n, nq, k, (dim + 127) / 128 * 128).merge_lds);
-          const int v = violation(n, nq, k, dim);
-          if (v && bad++ == 0) {
-            out[2] = n;
-            out[3] = nq;
-            out[4] = k;
-            out[5] = dim;
-            out[6] = v;
-          }
-        }
-  out[0] = points;
-  out[1] = max_lds;
-  return bad;
-}
+int64_t knn_plan_sweep(int64_t* out) { return sweep(false, out); }
+
+// The same grid and conditions over the plans of searches with per-query labels.
+int64_t knn_plan_sweep_labels(int64_t* out) { return sweep(true, out); }
 
 }  // extern "C"
 
