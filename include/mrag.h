@@ -96,6 +96,34 @@ int mrag_knn_set_labels(mrag_knn_index* index, const int64_t* rows, int64_t n, i
 /* Number of row ids handed out so far (live + deleted). */
 int mrag_knn_size(const mrag_knn_index* index, int64_t* n);
 
+/* Number of live rows (label != MRAG_LABEL_DELETED) among the ids handed out. */
+int mrag_knn_live_rows(const mrag_knn_index* index, int64_t* live);
+
+/* ---- K15: compaction ------------------------------------------------------
+ * The counterpart of Lance's table.optimize() / compact_files(): the per-row delete of
+ * an upsert (lancedb_store.py:91-92) only tombstones, and a re-ingested corpus keeps
+ * every dead row in the scan and in HBM until this is called.
+ * Remove the deleted rows, keeping the live ones in order: live row r becomes row remap[r]
+ * (the number of live rows before it), mrag_knn_size becomes the live count and the row buffers
+ * are reallocated to fit (a multiple of 768 rows, at least one tile; the bytes of a row are
+ * copied, so the index equals one that was given the live rows in order).
+ * remap: host int64 [old size] or NULL; deleted rows get -1. new_size (optional): the live count.
+ * With no deleted row nothing is reallocated or copied and remap is the identity. If the new
+ * buffers cannot be allocated the call returns MRAG_ERR_OOM with the index as it was.
+ * A mutation like mrag_knn_add: waits for searches in flight and excludes new ones. */
+int mrag_knn_compact(mrag_knn_index* index, int64_t* remap, int64_t* new_size);
+
+/* Timing of the last mrag_knn_compact on this handle (HIP events on the index's stream around
+ * the launches): K15a (remap) and K15b (gather) milliseconds and the bytes each read plus
+ * wrote; the gather's are 0 when nothing was deleted. Any pointer may be NULL. */
+int mrag_knn_compact_profile(const mrag_knn_index* index, double* remap_ms, double* gather_ms,
+                             int64_t* remap_bytes, int64_t* gather_bytes);
+
+/* building block (tests and timing): K15a alone on device pointers, labels int32 [n] ->
+ * remap int32 [n] (-1 for deleted), *live on the host after the call (the call waits for
+ * `stream`). labels and remap 16-byte aligned, n < 2^31. */
+int mrag_knn_row_remap(const int32_t* labels, int64_t n, int32_t* remap, int64_t* live, void* stream);
+
 /* Search nq queries (f32 [nq, dim]) for their k best rows among rows whose
  * label matches `label_filter`. out_scores f32 [nq, k], out_rows int64
  * [nq, k]; row ids are offset by `row_offset` (a shard's first global row).

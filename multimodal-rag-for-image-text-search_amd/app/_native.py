@@ -38,6 +38,11 @@ SIGNATURES = {
     "mrag_knn_add": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, ctypes.POINTER(_c_i64)]),
     "mrag_knn_set_labels": (_c_int, [_vp, _vp, _c_i64, _c_int]),
     "mrag_knn_size": (_c_int, [_vp, ctypes.POINTER(_c_i64)]),
+    "mrag_knn_live_rows": (_c_int, [_vp, ctypes.POINTER(_c_i64)]),
+    "mrag_knn_compact": (_c_int, [_vp, _vp, ctypes.POINTER(_c_i64)]),
+    "mrag_knn_compact_profile": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),
+    "mrag_knn_row_remap": (_c_int, [_vp, _c_i64, _vp, ctypes.POINTER(_c_i64), _vp]),
     "mrag_knn_search": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _c_i64, _vp, _vp, _vp, _c_int, _vp]),
     "mrag_knn_search_labels": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _vp]),
     "mrag_knn_last_stats": (_c_int, [_vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),

@@ -15,6 +15,9 @@ fp32 row segments + Parquet payloads + tombstones, atomic manifest) and are repl
 the GPU index with the same row ids. Processes sharing the directory (the reference's
 worker indexing while the API searches) see each other's commits: every search and upsert
 first replays what was committed since, and upserts serialise on a file lock.
+Deleted rows stay (in HBM, in the scan and on disk) until ``LanceDBStore.optimize()``, the
+counterpart of Lance's ``table.optimize()``: it compacts the index (K15), the host lists and
+the files to the live rows, in order; nothing calls it automatically.
 Semantics pinned in DESIGN.md §3: exact flat cosine (no IVF_PQ — the reference's
 index build is attempted on an empty table and swallowed, :51-60), prefilter, order
 (score desc, row asc), ``limit(max(top_k, 1))``, ``score = 1 - f32(1 - cos)``.
@@ -70,6 +73,7 @@ class _Table:
         self.lock = threading.RLock()
         self._seen_segments = 0    # committed segments replayed into this process
         self._seen_tombstones = 0  # committed tombstones applied
+        self._seen_generation = 0  # the files' generation they belong to (in memory: compactions so far)
 
     def _ensure_index(self, dim: int):
         if self.index is None:
@@ -106,11 +110,36 @@ class _Table:
                 if not rows:
                     del self.by_chunk[self.chunk_ids[r]]
 
+    def _reset(self) -> None:
+        """Forget the replayed rows (the user -> label map stays: labels only have to be stable
+        inside one process)."""
+        if self.index is not None:
+            self.index.close()
+        self.index = None
+        self.chunk_ids, self.metas, self.doc_ids, self.by_chunk = [], [], [], {}
+        self._seen_segments = self._seen_tombstones = 0
+
     def _sync(self) -> None:
-        """Replay the segments + tombstones committed (by any process) since the last sync."""
+        """Replay the segments + tombstones committed (by any process) since the last sync; after
+        another process's compaction (a new generation), drop everything and replay that
+        generation from the start, so that row ids are the compacted order here too."""
         if self.files is None:
             return
         self.files.refresh()
+        for _ in range(8):
+            try:
+                return self._replay()
+            except FileNotFoundError:
+                # the manifest read above was replaced by a compaction that has since removed a
+                # file it listed: read the new manifest and replay that
+                if not self.files.refresh():
+                    raise
+        self._replay()
+
+    def _replay(self) -> None:
+        if self.files.generation != self._seen_generation:
+            self._reset()
+            self._seen_generation = self.files.generation
         m = self.files.manifest
         if len(m["segments"]) > self._seen_segments:
             self._ensure_index(self.files.dim)
@@ -123,6 +152,43 @@ class _Table:
             self._seen_tombstones = m["tombstones"]
 
     _load = _sync  # name used by app.retrieval
+
+    def compact(self) -> Dict[str, int]:
+        """Remove the deleted rows from the index, the host lists and the files (the live rows keep
+        their order; row ids become dense). Returns rows_before / rows_after / generation."""
+        with self.lock:
+            with (self.files.write_lock() if self.files is not None else contextlib.nullcontext()):
+                self._sync()  # under the writer lock: what is compacted is what is committed
+                before = len(self.index) if self.index is not None else 0
+                if self.index is None or self.index.live_rows() == before:
+                    return {"rows_before": before, "rows_after": before, "generation": self._seen_generation}
+                remap = self.index.compact()
+                try:
+                    live = np.flatnonzero(remap >= 0)  # ascending old ids = ascending new ids
+                    self.chunk_ids = [self.chunk_ids[r] for r in live]
+                    self.metas = [self.metas[r] for r in live]
+                    self.doc_ids = [self.doc_ids[r] for r in live]
+                    self.by_chunk = {cid: [int(remap[r]) for r in rows] for cid, rows in self.by_chunk.items()}
+                    if self.files is not None:
+                        self._seen_generation = self.files.compact(remap)  # the commit
+                        self._seen_segments = len(self.files.manifest["segments"])
+                        self._seen_tombstones = 0
+                    else:
+                        self._seen_generation += 1
+                except BaseException:
+                    # the files still hold the old table: replay it on the next call
+                    if self.files is not None:
+                        self._reset()
+                        self._seen_generation = -1
+                    raise
+                return {"rows_before": before, "rows_after": len(self.index), "generation": self._seen_generation}
+
+    def dead_fraction(self) -> float:
+        """Deleted rows / rows handed out, of what is committed now (0 for an empty table)."""
+        with self.lock:
+            self._sync()
+            n = len(self.index) if self.index is not None else 0
+            return (n - self.index.live_rows()) / n if n else 0.0
 
     def upsert(self, payloads: List[Dict[str, Any]], vectors: Optional[np.ndarray] = None,
                staged: Optional[str] = None) -> None:
@@ -296,6 +362,23 @@ class LanceDBStore:
 
     def upsert_image_vectors(self, rows: Iterable[VectorRow]) -> None:
         self._upsert(self._image_table, rows)
+
+    def optimize(self, min_dead_fraction: float = 0.0) -> Dict[str, Dict[str, int]]:
+        """Reclaim the rows that upserts deleted, as Lance's ``table.optimize()`` does: each table
+        with at least one deleted row and more than ``min_dead_fraction`` of its rows deleted is
+        compacted (GPU index, host lists, files). Per table: ``rows_before``, ``rows_after`` and
+        the ``generation`` it is at afterwards (unchanged for a table left alone). Answers do not
+        change; other processes on the directory pick the compacted table up at their next call."""
+        out = {}
+        for table in (self._text_table, self._image_table):
+            with table.lock:
+                frac = table.dead_fraction()
+                if frac > 0.0 and frac > float(min_dead_fraction):
+                    out[table.name] = table.compact()
+                else:
+                    n = len(table.index) if table.index is not None else 0
+                    out[table.name] = {"rows_before": n, "rows_after": n, "generation": table._seen_generation}
+        return out
 
     def search_text(self, user_id: str, query_vec: Sequence[float], top_k: int) -> List[Dict[str, Any]]:
         return self._format_results(self._text_table.search(user_id, self._normalize(query_vec), max(top_k, 1)))

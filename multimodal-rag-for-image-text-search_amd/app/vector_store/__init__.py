@@ -41,7 +41,7 @@ class FlatIndex:
     """Exact flat cosine index of fixed ``dim`` on one GPU (one Lance table or one shard).
 
     Row ids are assigned densely in insertion order; ``delete`` tombstones rows
-    (their ids are not reused). Each row carries an int32 label (the host maps
+    (their ids are not reused; ``compact`` removes them and renumbers the rest). Each row carries an int32 label (the host maps
     ``user_id`` strings to labels); ``search(..., label=L)`` is the reference's
     ``where("user_id == ...")`` prefilter.
     """
@@ -118,6 +118,33 @@ class FlatIndex:
 
     def delete(self, rows: Sequence[int]) -> None:
         self.set_labels(rows, LABEL_DELETED)
+
+    def live_rows(self) -> int:
+        """Rows not deleted among the ``len(self)`` ids handed out."""
+        n = ctypes.c_int64(0)
+        _native.call("mrag_knn_live_rows", self._h, ctypes.byref(n))
+        return int(n.value)
+
+    def compact(self) -> np.ndarray:
+        """Remove the deleted rows (K15, ``mrag_knn_compact``): the live rows keep their order and
+        are renumbered densely, ``len(self)`` becomes the live count and the HBM buffers shrink to
+        fit. Returns the int64 remap of the old size: ``remap[old_row]`` is the row's new id, -1
+        for a deleted row. Afterwards the index answers every search as a fresh index that was
+        given the live rows in order would. With nothing deleted it is the identity and nothing
+        is reallocated. Searches may run beside it (they see the index before or after); an
+        ``add`` from another thread may not (the remap is sized before the call)."""
+        remap = np.empty(len(self), dtype=np.int64)
+        size = ctypes.c_int64(0)
+        _native.call("mrag_knn_compact", self._h, remap.ctypes.data, ctypes.byref(size))
+        return remap
+
+    def compact_profile(self) -> Tuple[float, float, int, int]:
+        """(K15a ms, K15b ms, K15a bytes, K15b bytes) of the last ``compact`` (HIP events)."""
+        a, b = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        ba, bb = ctypes.c_int64(0), ctypes.c_int64(0)
+        _native.call("mrag_knn_compact_profile", self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(ba),
+                     ctypes.byref(bb))
+        return float(a.value), float(b.value), int(ba.value), int(bb.value)
 
     # ------------------------------------------------------------------ search
     def search(self, queries: ArrayLike, k: int, label: Union[int, ArrayLike] = LABEL_ANY, row_offset: int = 0,

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "common.h"
+#include "knn_compact.h"
 #include "knn_generic.h"
 #include "knn_plan.h"
 
@@ -1971,6 +1972,10 @@ struct mrag_knn_index {
   DevBuf x16, x32, xn, labels;
   hipStream_t stream = nullptr;
   DevBuf stage_rows, stage_labels, rowlist;  // mutation staging
+  DevBuf remap, remap_scratch;               // K15a's output and its block sums (compact / live_rows)
+  hipEvent_t cev[3] = {nullptr, nullptr, nullptr};  // around K15a and K15b of the last compaction
+  double compact_ms[2] = {0.0, 0.0};                // their times (mrag_knn_compact_profile)
+  int64_t compact_bytes[2] = {0, 0};                // and the bytes each read plus wrote
   std::mutex pool_mu;                        // guards the context pool and the stats below
   std::vector<SearchCtx*> ctx_all, ctx_free;
   int64_t last_uncertified = 0, last_retries = 0;
@@ -1985,6 +1990,8 @@ struct mrag_knn_index {
   // with `device` current and nothing in flight (mrag_knn_destroy); the DevBufs free themselves
   ~mrag_knn_index() {
     for (SearchCtx* c : ctx_all) delete c;
+    for (hipEvent_t e : cev)
+      if (e) (void)hipEventDestroy(e);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -2069,6 +2076,103 @@ int grow(mrag_knn_index* ix, int64_t need) {
   ix->xn = std::move(nxn);
   ix->labels = std::move(nlab);
   ix->cap = ncap;
+  return MRAG_OK;
+}
+
+// K15a over the rows handed out: ix->remap gets the remap, *live the live count. Enqueues on the
+// index's stream and waits; the caller holds ix->mu.
+int remap_rows(mrag_knn_index* ix, int64_t* live) {
+  *live = 0;
+  if (ix->n == 0) return MRAG_OK;
+  if (int rc = ensure(ix->remap, (size_t)ix->n * 4)) return rc;
+  if (int rc = ensure(ix->remap_scratch, mrag_knn::remap_scratch_words(ix->n) * 4)) return rc;
+  int32_t* scratch = (int32_t*)ix->remap_scratch.p;  // [0]: the live count; from word 4: the block sums
+  hipStream_t s = ix->stream;
+  mrag::StreamDrain drain(s);
+  if (ix->cev[0]) MRAG_HIP(hipEventRecord(ix->cev[0], s));
+  if (int rc = mrag_knn::row_remap((const int32_t*)ix->labels.p, ix->n, (int32_t*)ix->remap.p, scratch, scratch + 4, s))
+    return rc;
+  if (ix->cev[1]) MRAG_HIP(hipEventRecord(ix->cev[1], s));
+  int32_t got = 0;
+  MRAG_HIP(hipMemcpyAsync(&got, scratch, 4, hipMemcpyDeviceToHost, s));
+  MRAG_HIP(hipStreamSynchronize(s));
+  drain.armed = false;
+  *live = got;
+  return MRAG_OK;
+}
+
+// The compaction proper: K15a, then (if any row is dead) new right-sized buffers, K15b and the
+// swap. The caller holds both locks. A failed allocation leaves the index as it was.
+int compact_rows(mrag_knn_index* ix, int64_t* remap_out, int64_t* new_size) {
+  const int64_t n = ix->n;
+  hipStream_t s = ix->stream;
+  for (hipEvent_t& e : ix->cev)
+    if (!e) MRAG_HIP(hipEventCreate(&e));
+  int64_t live = 0;
+  if (int rc = remap_rows(ix, &live)) return rc;
+  float ms = 0.0f;
+  if (n > 0) MRAG_HIP(hipEventElapsedTime(&ms, ix->cev[0], ix->cev[1]));
+  ix->compact_ms[0] = ms;
+  ix->compact_bytes[0] = n * 12;  // the labels twice, the remap once
+  if (live < n) {
+    const int DP = ix->DP;
+    int64_t ncap = std::max<int64_t>((int64_t)TILE_ROWS, live);
+    ncap = (ncap + 767) / 768 * 768;  // grow()'s rule
+    DevBuf nx16, nx32, nxn, nlab;     // an error return frees what was allocated so far
+    if (int rc = ensure(nx16, (size_t)ncap * DP * 2)) return rc;
+    if (int rc = ensure(nx32, (size_t)ncap * DP * 4)) return rc;
+    if (int rc = ensure(nxn, (size_t)ncap * 8)) return rc;
+    if (int rc = ensure(nlab, (size_t)ncap * 4)) return rc;
+    mrag::StreamDrain drain(s);  // nothing queued may outlive the new buffers on an error return
+    const int64_t tail = ncap - live;  // zeroed and labelled deleted, as grow() leaves it
+    if (tail > 0) {
+      MRAG_HIP(hipMemsetAsync((_Float16*)nx16.p + live * DP, 0, (size_t)tail * DP * 2, s));
+      MRAG_HIP(hipMemsetAsync((float*)nx32.p + live * DP, 0, (size_t)tail * DP * 4, s));
+      MRAG_HIP(hipMemsetAsync((double*)nxn.p + live, 0, (size_t)tail * 8, s));
+      hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)((tail + 255) / 256)), dim3(256), 0, s,
+                         (int32_t*)nlab.p + live, tail, (int32_t)MRAG_LABEL_DELETED);
+      MRAG_CHECK_LAUNCH();
+    }
+    mrag_knn::GatherRows g;
+    g.x16 = (const _Float16*)ix->x16.p;
+    g.x32 = (const float*)ix->x32.p;
+    g.xn = (const double*)ix->xn.p;
+    g.labels = (const int32_t*)ix->labels.p;
+    g.remap = (const int32_t*)ix->remap.p;
+    g.n = n;
+    g.DP = DP;
+    g.out_x16 = (_Float16*)nx16.p;
+    g.out_x32 = (float*)nx32.p;
+    g.out_xn = (double*)nxn.p;
+    g.out_labels = (int32_t*)nlab.p;
+    MRAG_HIP(hipEventRecord(ix->cev[1], s));
+    if (int rc = mrag_knn::gather_rows(g, s)) return rc;
+    MRAG_HIP(hipEventRecord(ix->cev[2], s));
+    MRAG_HIP(hipStreamSynchronize(s));
+    drain.armed = false;
+    MRAG_HIP(hipEventElapsedTime(&ms, ix->cev[1], ix->cev[2]));
+    ix->compact_ms[1] = ms;
+    ix->compact_bytes[1] = 2 * live * ((int64_t)DP * 6 + 12) + n * 4;
+    ix->x16 = std::move(nx16);  // frees the old buffers
+    ix->x32 = std::move(nx32);
+    ix->xn = std::move(nxn);
+    ix->labels = std::move(nlab);
+    ix->cap = ncap;
+    ix->n = live;
+  } else {
+    ix->compact_ms[1] = 0.0;
+    ix->compact_bytes[1] = 0;
+  }
+  if (remap_out && n > 0) {  // the device remap is int32 (n < 2^31); the ABI's is int64
+    if (live == n) {
+      for (int64_t i = 0; i < n; ++i) remap_out[i] = i;
+    } else {
+      std::vector<int32_t> h((size_t)n);
+      MRAG_HIP(hipMemcpy(h.data(), ix->remap.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < n; ++i) remap_out[i] = h[(size_t)i];
+    }
+  }
+  if (new_size) *new_size = live;
   return MRAG_OK;
 }
 
@@ -2601,6 +2705,34 @@ int mrag_knn_set_labels(mrag_knn_index* ix, const int64_t* rows, int64_t n, int3
                      (int32_t*)ix->labels.p, (const int64_t*)ix->rowlist.p, n, label);
   MRAG_CHECK_LAUNCH();
   MRAG_HIP(hipStreamSynchronize(ix->stream));
+  return MRAG_OK;
+}
+
+int mrag_knn_live_rows(const mrag_knn_index* cix, int64_t* live) {
+  MRAG_REQUIRE(cix != nullptr && live != nullptr, "NULL argument");
+  mrag_knn_index* ix = const_cast<mrag_knn_index*>(cix);
+  std::lock_guard<std::mutex> lk(ix->mu);  // no mutation meanwhile; searches only read the labels
+  mrag::DeviceGuard g(ix->device);
+  return remap_rows(ix, live);
+}
+
+int mrag_knn_compact(mrag_knn_index* ix, int64_t* remap, int64_t* new_size) {
+  MRAG_REQUIRE(ix != nullptr, "NULL index");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  std::unique_lock<std::shared_mutex> wl(ix->rw);
+  mrag::DeviceGuard g(ix->device);
+  return compact_rows(ix, remap, new_size);
+}
+
+int mrag_knn_compact_profile(const mrag_knn_index* cix, double* remap_ms, double* gather_ms, int64_t* remap_bytes,
+                             int64_t* gather_bytes) {
+  MRAG_REQUIRE(cix != nullptr, "NULL index");
+  mrag_knn_index* ix = const_cast<mrag_knn_index*>(cix);
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (remap_ms) *remap_ms = ix->compact_ms[0];
+  if (gather_ms) *gather_ms = ix->compact_ms[1];
+  if (remap_bytes) *remap_bytes = ix->compact_bytes[0];
+  if (gather_bytes) *gather_bytes = ix->compact_bytes[1];
   return MRAG_OK;
 }
 
