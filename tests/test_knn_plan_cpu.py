@@ -189,3 +189,22 @@ def test_paths_of_test_knn_sample_count_gpu(plan_lib):
             assert p["idbits"] <= REC_ID_BITS_MAX
     # the shape the band cases used to run at 512 dims never reached a sampled tile
     assert P(140_000, 1000, 12, 512)["sampled"] == 0
+
+
+def test_paths_of_test_knn_path_edges_gpu(plan_lib):
+    P = lambda *a: _plan(plan_lib, *a)  # noqa: E731
+    # test_v1_at_depth: v1 at list depths 32, 16, 16, 8, k up to MAX_K, one and two query groups,
+    # more tiles than splits (six per split on the 100k-row table)
+    for dim, kl in ((100, 32), (256, 16), (384, 16), (512, 8)):
+        for k in (65, 128, 256):
+            for nq in (1, 33, 257):
+                p = P(20_000, nq, k, dim)
+                assert (p["path"], p["KL"], p["qgroups"]) == (V1, kl, 2 if nq > 256 else 1), (dim, k, nq, p)
+                assert p["ntiles"] > p["S"] and p["M"] == k + 32
+    p = P(100_000, 33, 256, 256)
+    assert p["path"] == V1 and p["ntiles"] >= 6 * p["S"]
+    # test_both_sides_of_a_switch_agree: v3 | v1 at 64 | 65, v1 | K7g at 256 | 257
+    for dim in (128, 512):
+        assert [P(20_000, 40, k, dim)["path"] for k in (64, 65, 256, 257)] == [V3, V1, V1, GENERIC]
+    # test_peaked_and_scaled_rows: v3 and v1
+    assert P(40_050, 16, 10, 384)["path"] == V3 and P(40_050, 16, 100, 384)["path"] == V1
