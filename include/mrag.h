@@ -153,6 +153,45 @@ int mrag_knn_search_labels(mrag_knn_index* index, const float* queries, int64_t 
                            const int32_t* label_filters, int64_t row_offset, float* out_scores,
                            double* out_scores64, int64_t* out_rows, int32_t ptr_kind, void* stream);
 
+/* ---- K16: diverse top-k by maximal marginal relevance -------
+ * The largest fetch_k / candidate count per query: K16 keeps a query's candidates in LDS. */
+#define MRAG_KNN_MMR_MAX_FETCH 1024
+
+/* Search with diversity. Per query: the fetch_k best rows of mrag_knn_search /
+ * mrag_knn_search_labels under the query's filter (label_filters, int32 [nq], when not NULL,
+ * else label_filter for every query) are the candidates; step 0 selects the best of them, and
+ * every later step the unselected candidate with the largest
+ *   lambda * score - (1 - lambda) * max over the selected rows j of cos(x, x_j)
+ * in f64 (the cosine between two stored rows as the search computes a score, 0 on a zero
+ * norm; ties go to the candidate that the search ranks first). Outputs as mrag_knn_search:
+ * [nq, k] in selection order, the scores being the rows' relevance scores as the search
+ * returns them; -inf / -1 past the candidates. lambda = 1 is mrag_knn_search(k), bit for bit.
+ * The search, the selection and the gather of the outputs run on one stream under one shared
+ * lock, so a mutation (add, set_labels, compact) never falls between them; the search keeps
+ * its plan, its kernels and its mrag_knn_last_stats.
+ * 1 <= k <= fetch_k <= MRAG_KNN_MMR_MAX_FETCH, lambda finite in [0, 1], no NULL pointer but
+ * the optional ones: otherwise MRAG_ERR_ARG, with a message naming the argument, before any
+ * HIP call. nq = 0 returns MRAG_OK. Thread-safe like mrag_knn_search. */
+int mrag_knn_search_mmr(mrag_knn_index* index, const float* queries, int64_t nq, int32_t k,
+                        int32_t fetch_k, double lambda, int32_t label_filter,
+                        const int32_t* label_filters, int64_t row_offset, float* out_scores,
+                        double* out_scores64, int64_t* out_rows, int32_t ptr_kind, void* stream);
+
+/* K16 alone, on candidates the caller supplies: cand_rows int64 [nq, m] (row ids of this
+ * index without any row_offset; -1 marks an empty slot) and cand_scores64 f64 [nq, m], e.g.
+ * the output of mrag_knn_search(k = m, out_scores64). A slot takes part when its row is >= 0
+ * and its score above -inf; step 0 selects the first such slot. out_pos int32 [nq, k]: the
+ * selected candidate positions in selection order, -1 once the candidates run out;
+ * out_value64 (optional) f64 [nq, k]: the value each was selected with (lambda * score at step
+ * 0, -inf for -1). All data pointers share ptr_kind. Takes the index's shared lock and
+ * returns once the selection is done. A row id >= mrag_knn_size is MRAG_ERR_ARG (a host
+ * array is checked before any launch; a device array by the kernel, which never reads such
+ * a row). 1 <= k <= m <= MRAG_KNN_MMR_MAX_FETCH and lambda as above. */
+int mrag_knn_mmr_select(mrag_knn_index* index, const int64_t* cand_rows,
+                        const double* cand_scores64, int64_t nq, int32_t m, int32_t k,
+                        double lambda, int32_t* out_pos, double* out_value64, int32_t ptr_kind,
+                        void* stream);
+
 /* Statistics of the last search on this handle: number of queries whose fp16
  * candidate pass could not be certified exact and went through the
  * threshold-collect pass, and how many collect retries overflowed. */

@@ -45,6 +45,9 @@ SIGNATURES = {
     "mrag_knn_row_remap": (_c_int, [_vp, _c_i64, _vp, ctypes.POINTER(_c_i64), _vp]),
     "mrag_knn_search": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _c_i64, _vp, _vp, _vp, _c_int, _vp]),
     "mrag_knn_search_labels": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _vp]),
+    "mrag_knn_search_mmr": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, ctypes.c_double, _c_int, _vp, _c_i64, _vp, _vp,
+                                     _vp, _c_int, _vp]),
+    "mrag_knn_mmr_select": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _c_int, ctypes.c_double, _vp, _vp, _c_int, _vp]),
     "mrag_knn_last_stats": (_c_int, [_vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),
     "mrag_knn_profile": (_c_int, [_vp, _c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64)]),
     "mrag_topk_merge": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _vp, _vp, _vp, _vp]),

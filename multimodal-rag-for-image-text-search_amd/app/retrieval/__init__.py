@@ -34,12 +34,18 @@ def _user_list(user_id: Union[str, Sequence[str]], n: int) -> Optional[List[str]
 
 
 def search_batch(modality: str, user_id: Union[str, Sequence[str]], query_vecs: np.ndarray,
-                 top_k: int) -> List[List[Dict[str, Any]]]:
+                 top_k: int, mmr_lambda: Optional[float] = None,
+                 fetch_k: Optional[int] = None) -> List[List[Dict[str, Any]]]:
     """Raw hits ({chunk_id, score, meta}) for every row of ``query_vecs``, one GPU launch.
 
     ``user_id`` is one user for the whole batch or a sequence of one user per query: a batch a
     multi-user server collected from concurrent requests is still one scan, each query filtered
-    to its own user's rows (a user the table has never seen gets ``[]``)."""
+    to its own user's rows (a user the table has never seen gets ``[]``).
+
+    ``mmr_lambda`` (default None: the plain search): the hits of every query are chosen for
+    diversity by maximal marginal relevance among its ``fetch_k`` best (default
+    ``min(4 top_k, 1024)``), still in the one launch (``FlatIndex.search_mmr``); they come in
+    selection order."""
     store, _ = _store()
     table = store._text_table if modality == "text" else store._image_table
     q = np.asarray(query_vecs, dtype=np.float32)
@@ -59,12 +65,15 @@ def search_batch(modality: str, user_id: Union[str, Sequence[str]], query_vecs: 
             label = np.array([table.labels.get(u, len(table.labels)) for u in users], dtype=np.int32)
             if table.index is None or len(q) == 0:
                 return [[] for _ in range(len(q))]
-        s, r = table.index.search(q, max(int(top_k), 1), label=label)
+        if mmr_lambda is None:
+            s, r = table.index.search(q, max(int(top_k), 1), label=label)
+        else:
+            s, r = table.index.search_mmr(q, max(int(top_k), 1), fetch_k=fetch_k, lam=float(mmr_lambda), label=label)
         out = []
         for i in range(len(q)):
             rows = [{"chunk_id": table.chunk_ids[row], "_distance": np.float32(1.0) - np.float32(sc),
                      "meta": table.metas[row]} for sc, row in zip(s[i], r[i]) if row >= 0]
-            out.append(store._format_results(rows))
+            out.append(store._format_results(rows, keep_order=mmr_lambda is not None))
         return out
 
 
@@ -82,12 +91,17 @@ def _branch_pool():
 
 
 def retrieve_batch(user_id: Union[str, Sequence[str]], queries: Sequence[str], top_k_text: Optional[int] = None,
-                   top_k_image: Optional[int] = None, rerank: Optional[bool] = None) -> List[List[Dict[str, Any]]]:
+                   top_k_image: Optional[int] = None, rerank: Optional[bool] = None,
+                   mmr_lambda: Optional[float] = None,
+                   mmr_fetch_k: Optional[int] = None) -> List[List[Dict[str, Any]]]:
     """Fused text+image results per query, batched end to end = ``retrieve(user_id, q)``
     (app/ml/retrieve.py:103-117) for every q. ``rerank`` defaults to RERANK_ENABLED; the
     cross-encoder is ``retrieve._get_cross_encoder()`` (False -> no rerank, as retrieve).
     ``user_id`` is one user or one per query (``search_batch``): result i then equals
     ``retrieve_batch(user_id[i], [queries[i]], ...)[0]``.
+
+    ``mmr_lambda`` (default None: as before): each modality's search picks its hits for
+    diversity (``search_batch(..., mmr_lambda, mmr_fetch_k)``), before rerank and fusion.
 
     The image branch (CLIP text tower -> image search) runs in a worker thread beside the text
     branch (MiniLM -> text search): each native call returns to its own thread only, so the two
@@ -107,12 +121,12 @@ def retrieve_batch(user_id: Union[str, Sequence[str]], queries: Sequence[str], t
         img_vecs = _normalize(_to_numpy(model.get_text_features(**proc(text=qs))))
         blank = np.array([not q.strip() for q in qs])
         img_vecs[blank] = 0.0
-        return search_batch("image", user_id, img_vecs, ik)
+        return search_batch("image", user_id, img_vecs, ik, mmr_lambda=mmr_lambda, fetch_k=mmr_fetch_k)
 
     fut = _branch_pool().submit(image_branch)
     try:
         text_vecs = r.embed_text_batch(qs)
-        th = search_batch("text", user_id, text_vecs, tk)
+        th = search_batch("text", user_id, text_vecs, tk, mmr_lambda=mmr_lambda, fetch_k=mmr_fetch_k)
     except BaseException as text_err:
         # the text branch's error is the one raised; wait for the image branch first (it shares
         # the GPU and the store) and chain its error, if any, instead of replacing this one

@@ -225,7 +225,10 @@ class _Table:
                 self._append_rows(emb, [p["user_id"] for p in payloads], [p["chunk_id"] for p in payloads],
                                   [p["meta"] for p in payloads], [p["document_id"] for p in payloads])
 
-    def search(self, user_id: str, vector: List[float], k: int) -> List[Dict[str, Any]]:
+    def search(self, user_id: str, vector: List[float], k: int, mmr_lambda: Optional[float] = None,
+               fetch_k: Optional[int] = None) -> List[Dict[str, Any]]:
+        """``mmr_lambda`` not None: the k rows are chosen for diversity among the ``fetch_k`` best
+        (``FlatIndex.search_mmr``) and come in selection order."""
         with self.lock:
             self._sync()
             label = self.labels.get(user_id)
@@ -234,7 +237,10 @@ class _Table:
             q = np.asarray(vector, dtype=np.float32)[None, :]
             if q.shape[1] != self.dim:
                 raise ValueError(f"{self.name}: query dim {q.shape[1]} != table dim {self.dim}")
-            s, r = self.index.search(q, k, label=label)
+            if mmr_lambda is None:
+                s, r = self.index.search(q, k, label=label)
+            else:
+                s, r = self.index.search_mmr(q, k, fetch_k=fetch_k, lam=float(mmr_lambda), label=label)
             rows = []
             for score, row in zip(s[0], r[0]):
                 if row < 0:
@@ -380,14 +386,27 @@ class LanceDBStore:
                     out[table.name] = {"rows_before": n, "rows_after": n, "generation": table._seen_generation}
         return out
 
-    def search_text(self, user_id: str, query_vec: Sequence[float], top_k: int) -> List[Dict[str, Any]]:
-        return self._format_results(self._text_table.search(user_id, self._normalize(query_vec), max(top_k, 1)))
+    def search_text(self, user_id: str, query_vec: Sequence[float], top_k: int, *,
+                    mmr_lambda: Optional[float] = None, fetch_k: Optional[int] = None) -> List[Dict[str, Any]]:
+        """``mmr_lambda`` (keyword only, default None: the plain search): choose the hits for
+        diversity by maximal marginal relevance among the ``fetch_k`` best (default
+        ``min(4 top_k, 1024)``); they come in selection order, not sorted by score."""
+        return self._search(self._text_table, user_id, query_vec, top_k, mmr_lambda, fetch_k)
 
-    def search_image(self, user_id: str, query_vec: Sequence[float], top_k: int) -> List[Dict[str, Any]]:
-        return self._format_results(self._image_table.search(user_id, self._normalize(query_vec), max(top_k, 1)))
+    def search_image(self, user_id: str, query_vec: Sequence[float], top_k: int, *,
+                     mmr_lambda: Optional[float] = None, fetch_k: Optional[int] = None) -> List[Dict[str, Any]]:
+        """As ``search_text``, on the image collection."""
+        return self._search(self._image_table, user_id, query_vec, top_k, mmr_lambda, fetch_k)
+
+    def _search(self, table: "_Table", user_id, query_vec, top_k, mmr_lambda, fetch_k) -> List[Dict[str, Any]]:
+        if mmr_lambda is None:
+            return self._format_results(table.search(user_id, self._normalize(query_vec), max(top_k, 1)))
+        rows = table.search(user_id, self._normalize(query_vec), max(top_k, 1), mmr_lambda=mmr_lambda,
+                            fetch_k=fetch_k)
+        return self._format_results(rows, keep_order=True)
 
     @staticmethod
-    def _format_results(rows: List[Dict[str, Any]]) -> List[Dict[str, Any]]:
+    def _format_results(rows: List[Dict[str, Any]], keep_order: bool = False) -> List[Dict[str, Any]]:
         out = [
             {
                 "chunk_id": row.get("chunk_id"),
@@ -396,7 +415,8 @@ class LanceDBStore:
             }
             for row in rows
         ]
-        out.sort(key=lambda item: item["score"], reverse=True)
+        if not keep_order:  # MMR hits stay in selection order
+            out.sort(key=lambda item: item["score"], reverse=True)
         return out
 
     @staticmethod

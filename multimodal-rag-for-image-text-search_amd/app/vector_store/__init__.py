@@ -23,6 +23,7 @@ ArrayLike = Union[np.ndarray, "torch.Tensor"]  # noqa: F821
 
 MAX_DIM = 4096  # K7/K8 fused scan up to 512; K7g (knn_generic.hip) above
 MAX_K = 65536
+MMR_MAX_FETCH = 1024  # MRAG_KNN_MMR_MAX_FETCH: K16 keeps a query's candidates in LDS
 LABEL_ANY = _native.MRAG_LABEL_ANY
 LABEL_DELETED = _native.MRAG_LABEL_DELETED
 
@@ -244,6 +245,99 @@ class FlatIndex:
                      _native.MRAG_PTR_HOST, None)
         return (s, r, s64) if with_f64 else (s, r)
 
+    # ------------------------------------------------------------------ diversity (K16)
+    def search_mmr(self, queries: ArrayLike, k: int, fetch_k: Optional[int] = None, lam: float = 0.5,
+                   label: Union[int, ArrayLike] = LABEL_ANY, row_offset: int = 0, with_f64: bool = False):
+        """``search`` with diversity: k rows per query chosen by maximal marginal relevance among
+        the ``fetch_k`` best (default ``min(4 k, 1024)``; at most ``MMR_MAX_FETCH``), in one
+        native call (``mrag_knn_search_mmr``). Step 0 takes the best row; every
+        later step the candidate with the largest ``lam * score - (1 - lam) * max cosine to a row
+        already taken``. ``lam = 1`` is ``search(queries, k)``; smaller values trade relevance
+        for spread. Returns what ``search`` returns, rows in selection order with their
+        relevance scores. ``label`` as in ``search`` (one filter, or one per query)."""
+        k = int(k)
+        fetch_k = min(4 * k, MMR_MAX_FETCH) if fetch_k is None else int(fetch_k)
+        row_offset = int(row_offset)
+        per_query = not isinstance(label, (int, np.integer))
+        if _is_torch(queries):
+            import torch
+
+            q = queries.detach().to(dtype=torch.float32).contiguous()
+            if q.ndim == 1:
+                q = q.unsqueeze(0)
+            if q.shape[1] != self.dim:
+                raise ValueError(f"queries must be [nq, {self.dim}]")
+            nq = q.shape[0]
+            lab = None
+            if per_query:
+                lab = torch.as_tensor(np.asarray(label) if not _is_torch(label) else label)
+                lab = lab.detach().reshape(-1).to(device=q.device, dtype=torch.int32).contiguous()
+                if lab.shape[0] != nq:
+                    raise ValueError(f"label must be an int or hold one filter per query ({nq}), got {lab.shape[0]}")
+                if nq and int(lab.min()) < LABEL_ANY:
+                    raise ValueError("label filters must be labels >= 0 or LABEL_ANY")
+            s = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=q.device)
+            r = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
+            s64 = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=q.device) if with_f64 else None
+            _native.call("mrag_knn_search_mmr", self._h, q.data_ptr(), nq, k, fetch_k, float(lam),
+                         LABEL_ANY if per_query else int(label), lab.data_ptr() if lab is not None else None,
+                         row_offset, s.data_ptr(), s64.data_ptr() if s64 is not None else None, r.data_ptr(),
+                         _native.MRAG_PTR_DEVICE, _stream_ptr(q))
+            return (s, r, s64) if with_f64 else (s, r)
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}], got {q.shape}")
+        nq = q.shape[0]
+        lab = None
+        if per_query:
+            if _is_torch(label):
+                label = label.detach().cpu().numpy()
+            lab = np.ascontiguousarray(np.asarray(label).reshape(-1), dtype=np.int32)
+            if lab.shape[0] != nq:
+                raise ValueError(f"label must be an int or hold one filter per query ({nq}), got {lab.shape[0]}")
+        s = np.empty((nq, max(k, 0)), dtype=np.float32)
+        r = np.empty((nq, max(k, 0)), dtype=np.int64)
+        s64 = np.empty((nq, max(k, 0)), dtype=np.float64) if with_f64 else None
+        _native.call("mrag_knn_search_mmr", self._h, q.ctypes.data, nq, k, fetch_k, float(lam),
+                     LABEL_ANY if per_query else int(label), lab.ctypes.data if lab is not None else None,
+                     row_offset, s.ctypes.data, s64.ctypes.data if s64 is not None else None, r.ctypes.data,
+                     _native.MRAG_PTR_HOST, None)
+        return (s, r, s64) if with_f64 else (s, r)
+
+    def mmr_select(self, rows: ArrayLike, scores64: ArrayLike, k: int, lam: float, with_values: bool = False):
+        """K16 alone (``mrag_knn_mmr_select``): ``rows`` int64 ``[nq, m]`` (row ids of this index,
+        -1 for an empty slot) and ``scores64`` f64 ``[nq, m]``, e.g. ``search(q, m, with_f64=True)``
+        without a ``row_offset``. Returns the selected candidate positions int32 ``[nq, k]`` in
+        selection order (-1 once the candidates run out) and, with ``with_values``, the f64 value
+        each was selected with. numpy in, numpy out; torch CUDA in, torch out."""
+        k = int(k)
+        if _is_torch(rows):
+            import torch
+
+            r = rows.detach().to(dtype=torch.int64).contiguous()
+            s64 = scores64.detach().to(device=r.device, dtype=torch.float64).contiguous()
+            if r.ndim != 2 or s64.shape != r.shape:
+                raise ValueError("rows and scores64 must both be [nq, m]")
+            nq, m = r.shape
+            pos = torch.empty((nq, max(k, 0)), dtype=torch.int32, device=r.device)
+            val = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=r.device) if with_values else None
+            _native.call("mrag_knn_mmr_select", self._h, r.data_ptr(), s64.data_ptr(), nq, m, k, float(lam),
+                         pos.data_ptr(), val.data_ptr() if val is not None else None, _native.MRAG_PTR_DEVICE,
+                         _stream_ptr(r))
+            return (pos, val) if with_values else pos
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        s64 = np.ascontiguousarray(scores64, dtype=np.float64)
+        if r.ndim != 2 or s64.shape != r.shape:
+            raise ValueError("rows and scores64 must both be [nq, m]")
+        nq, m = r.shape
+        pos = np.empty((nq, max(k, 0)), dtype=np.int32)
+        val = np.empty((nq, max(k, 0)), dtype=np.float64) if with_values else None
+        _native.call("mrag_knn_mmr_select", self._h, r.ctypes.data, s64.ctypes.data, nq, m, k, float(lam),
+                     pos.ctypes.data, val.ctypes.data if val is not None else None, _native.MRAG_PTR_HOST, None)
+        return (pos, val) if with_values else pos
+
     def profile(self, enable: int = -1) -> Tuple[float, int]:
         """Scan-kernel timing (HIP events on the search stream): enable=1 reset+on,
         0 off, -1 read. Returns (total scan ms, timed launches)."""
@@ -291,4 +385,4 @@ def l2norm_rows(x):
     return y
 
 
-__all__ = ["FlatIndex", "topk_merge", "l2norm_rows", "LABEL_ANY", "LABEL_DELETED"]
+__all__ = ["FlatIndex", "topk_merge", "l2norm_rows", "LABEL_ANY", "LABEL_DELETED", "MMR_MAX_FETCH"]

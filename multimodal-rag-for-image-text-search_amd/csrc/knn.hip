@@ -28,6 +28,7 @@
 //   xn     [cap]     f64    |x|
 //   labels [cap]     int32  user label, MRAG_LABEL_DELETED for tombstones / padding
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <mutex>
 #include <shared_mutex>
@@ -38,6 +39,7 @@
 #include "common.h"
 #include "knn_compact.h"
 #include "knn_generic.h"
+#include "knn_mmr.h"
 #include "knn_plan.h"
 
 #define AS1 __attribute__((address_space(1)))
@@ -1947,6 +1949,9 @@ struct SearchCtx {
   DevBuf qin, q32, qn, q16, part_s, part_i, thresh, fail_list, counters, cand_cnt, cand, scratch;
   DevBuf out_s, out_s64, out_r, theta, part_tau, rec;
   DevBuf qlab_in, qlab;  // labelled search: the filters as given (host arrays land here) / per query slot
+  // MMR (K16): the fetch search's output [nq][fetch_k], the selected positions [nq][k], their
+  // values, and the word K16 sets when a supplied candidate row is out of range
+  DevBuf mmr_s, mmr_s64, mmr_r, mmr_pos, mmr_v, mmr_flag;
   int32_t* host_counters = nullptr;  // pinned [2]: fail_cnt, overflow
   int32_t* host_fail = nullptr;      // coherent pinned [4]: [0] = some query failed K8's certificate
   hipEvent_t done = nullptr;         // end of the search's device work (waited by spinning)
@@ -2496,6 +2501,36 @@ int search_fused(const Search& q, const SearchPlan& p, SearchStats& st) {
   return MRAG_OK;
 }
 
+// One search along its plan: everything it enqueues on q.s, and the certificate round trip of
+// the fused path. The outputs are device pointers.
+int run_search(const Search& q, SearchStats& st) {
+  mrag_knn_index* ix = q.ix;
+  const int64_t nout = q.nq * q.k;
+  const SearchPlan plan = plan_search(ix->n, q.nq, q.k, ix->DP, q.label_filters != nullptr);
+  switch (plan.path) {
+    case SearchPath::Empty:
+      hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, q.s, q.os, q.os64,
+                         q.orr, nout);
+      MRAG_CHECK_LAUNCH();
+      break;
+    case SearchPath::Generic:
+      if (int rc = stage_queries(q, plan)) return rc;
+      if (int rc = mrag_knn::search_generic(generic_args(q), q.c->gws, q.s, nullptr)) return rc;
+      break;
+    default:
+      if (int rc = search_fused(q, plan, st)) return rc;
+  }
+  return MRAG_OK;
+}
+
+void publish_stats(mrag_knn_index* ix, SearchCtx* c, const SearchStats& st) {
+  std::lock_guard<std::mutex> lk(ix->pool_mu);
+  ix->last_uncertified = st.uncertified;
+  ix->last_retries = st.retries;
+  ix->last_ctx = c;
+  std::copy(st.info, st.info + 8, ix->last_info);
+}
+
 // mrag_knn_search (label_filters null: label_filter for every query) and mrag_knn_search_labels.
 int search_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k, int32_t label_filter,
                  const int32_t* label_filters, int64_t row_offset, float* out_scores, double* out_scores64,
@@ -2537,21 +2572,8 @@ int search_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k
   }
 
   const Search q{ix, c, s, queries, host, nq, k, label_filter, label_filters, row_offset, os, os64, orr, profile};
-  const SearchPlan plan = plan_search(ix->n, nq, k, ix->DP, label_filters != nullptr);
   SearchStats st;
-  switch (plan.path) {
-    case SearchPath::Empty:
-      hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, os, os64, orr,
-                         nout);
-      MRAG_CHECK_LAUNCH();
-      break;
-    case SearchPath::Generic:
-      if (int rc = stage_queries(q, plan)) return rc;
-      if (int rc = mrag_knn::search_generic(generic_args(q), c->gws, s, nullptr)) return rc;
-      break;
-    default:
-      if (int rc = search_fused(q, plan, st)) return rc;
-  }
+  if (int rc = run_search(q, st)) return rc;
 
   if (host) {
     MRAG_HIP(hipMemcpyAsync(out_scores, os, nout * 4, hipMemcpyDeviceToHost, s));
@@ -2560,11 +2582,166 @@ int search_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k
   }
   if (int rc = wait_stream(c, s)) return rc;
   drain.armed = false;
-  std::lock_guard<std::mutex> lk(ix->pool_mu);
-  ix->last_uncertified = st.uncertified;
-  ix->last_retries = st.retries;
-  ix->last_ctx = c;
-  std::copy(st.info, st.info + 8, ix->last_info);
+  publish_stats(ix, c, st);
+  return MRAG_OK;
+}
+
+mrag_knn::MmrSelect mmr_args(const mrag_knn_index* ix, const int64_t* rows, const double* s64, int64_t nq, int m,
+                             int k, double lam, int32_t* pos, double* v, int32_t* bad_row) {
+  mrag_knn::MmrSelect a{};
+  a.x32 = (const float*)ix->x32.p;
+  a.xn = (const double*)ix->xn.p;
+  a.n = ix->n;
+  a.D = ix->D;
+  a.DP = ix->DP;
+  a.cand_rows = rows;
+  a.cand_s64 = s64;
+  a.nq = nq;
+  a.m = m;
+  a.k = k;
+  a.lam = lam;
+  a.out_pos = pos;
+  a.out_v = v;
+  a.bad_row = bad_row;
+  return a;
+}
+
+// mrag_knn_search_mmr: the search with k = fetch_k into the context's buffers, K16, and the
+// gather of the selected slots into the outputs: one stream, one shared lock, one context.
+int search_mmr_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k, int32_t fetch_k, double lam,
+                     int32_t label_filter, const int32_t* label_filters, int64_t row_offset, float* out_scores,
+                     double* out_scores64, int64_t* out_rows, int32_t ptr_kind, void* stream_arg) {
+  std::shared_lock<std::shared_mutex> rl(ix->rw);
+  mrag::DeviceGuard g(ix->device);
+  SearchCtx* c = nullptr;
+  if (int rc = ctx_get(ix, &c)) return rc;
+  CtxLease lease{ix, c};
+  bool profile;
+  {
+    std::lock_guard<std::mutex> lk(ix->pool_mu);
+    profile = ix->profile;
+  }
+  hipStream_t s = stream_arg ? (hipStream_t)stream_arg : ix->stream;
+  const bool host = ptr_kind == MRAG_PTR_HOST;
+  if (!host && !stream_arg)
+    if (int rc = mrag::wait_null_stream(c->null_ev, s)) return rc;
+  mrag::StreamDrain drain(s);  // as in search_entry
+  const int64_t nout = nq * k, ncand = nq * fetch_k;
+
+  float* os = out_scores;
+  double* os64 = out_scores64;
+  int64_t* orr = out_rows;
+  if (host) {
+    if (int rc = ensure(c->out_s, nout * 4)) return rc;
+    if (int rc = ensure(c->out_r, nout * 8)) return rc;
+    os = (float*)c->out_s.p;
+    orr = (int64_t*)c->out_r.p;
+    if (out_scores64) {
+      if (int rc = ensure(c->out_s64, nout * 8)) return rc;
+      os64 = (double*)c->out_s64.p;
+    }
+  }
+  if (int rc = ensure(c->mmr_s, ncand * 4)) return rc;
+  if (int rc = ensure(c->mmr_s64, ncand * 8)) return rc;
+  if (int rc = ensure(c->mmr_r, ncand * 8)) return rc;
+  if (int rc = ensure(c->mmr_pos, nout * 4)) return rc;
+  float* cand_s = (float*)c->mmr_s.p;
+  double* cand_s64 = (double*)c->mmr_s64.p;
+  int64_t* cand_r = (int64_t*)c->mmr_r.p;
+  int32_t* pos = (int32_t*)c->mmr_pos.p;
+
+  // the candidates keep their local row ids: K16 reads the rows; the gather adds row_offset
+  const Search q{ix, c, s, queries, host, nq, fetch_k, label_filter, label_filters, 0, cand_s, cand_s64, cand_r,
+                 profile};
+  SearchStats st;
+  if (int rc = run_search(q, st)) return rc;
+  if (int rc = mrag_knn::mmr_select(mmr_args(ix, cand_r, cand_s64, nq, fetch_k, k, lam, pos, nullptr, nullptr), s))
+    return rc;
+  mrag_knn::MmrGather ga{};
+  ga.pos = pos;
+  ga.cand_s = cand_s;
+  ga.cand_s64 = cand_s64;
+  ga.cand_rows = cand_r;
+  ga.nq = nq;
+  ga.m = fetch_k;
+  ga.k = k;
+  ga.row_offset = row_offset;
+  ga.out_s = os;
+  ga.out_s64 = os64;
+  ga.out_r = orr;
+  if (int rc = mrag_knn::mmr_gather(ga, s)) return rc;
+
+  if (host) {
+    MRAG_HIP(hipMemcpyAsync(out_scores, os, nout * 4, hipMemcpyDeviceToHost, s));
+    MRAG_HIP(hipMemcpyAsync(out_rows, orr, nout * 8, hipMemcpyDeviceToHost, s));
+    if (out_scores64) MRAG_HIP(hipMemcpyAsync(out_scores64, os64, nout * 8, hipMemcpyDeviceToHost, s));
+  }
+  if (int rc = wait_stream(c, s)) return rc;
+  drain.armed = false;
+  publish_stats(ix, c, st);
+  return MRAG_OK;
+}
+
+// mrag_knn_mmr_select: K16 on the caller's candidates.
+int mmr_select_entry(mrag_knn_index* ix, const int64_t* cand_rows, const double* cand_scores64, int64_t nq, int32_t m,
+                     int32_t k, double lam, int32_t* out_pos, double* out_value64, int32_t ptr_kind,
+                     void* stream_arg) {
+  std::shared_lock<std::shared_mutex> rl(ix->rw);
+  const bool host = ptr_kind == MRAG_PTR_HOST;
+  const int64_t nout = nq * k, ncand = nq * m;
+  if (host)  // a device array is checked by the kernel (below)
+    for (int64_t i = 0; i < ncand; ++i)
+      MRAG_REQUIRE(cand_rows[i] < ix->n, "cand_rows: row %lld of query %lld is not below the index size %lld",
+                   (long long)cand_rows[i], (long long)(i / m), (long long)ix->n);
+  mrag::DeviceGuard g(ix->device);
+  SearchCtx* c = nullptr;
+  if (int rc = ctx_get(ix, &c)) return rc;
+  CtxLease lease{ix, c};
+  hipStream_t s = stream_arg ? (hipStream_t)stream_arg : ix->stream;
+  if (!host && !stream_arg)
+    if (int rc = mrag::wait_null_stream(c->null_ev, s)) return rc;
+  mrag::StreamDrain drain(s);
+
+  const int64_t* rows = cand_rows;
+  const double* s64 = cand_scores64;
+  int32_t* pos = out_pos;
+  double* val = out_value64;
+  if (int rc = ensure(c->mmr_flag, 16)) return rc;
+  if (host) {
+    if (int rc = ensure(c->mmr_r, ncand * 8)) return rc;
+    if (int rc = ensure(c->mmr_s64, ncand * 8)) return rc;
+    if (int rc = ensure(c->mmr_pos, nout * 4)) return rc;
+    MRAG_HIP(hipMemcpyAsync(c->mmr_r.p, cand_rows, ncand * 8, hipMemcpyHostToDevice, s));
+    MRAG_HIP(hipMemcpyAsync(c->mmr_s64.p, cand_scores64, ncand * 8, hipMemcpyHostToDevice, s));
+    rows = (const int64_t*)c->mmr_r.p;
+    s64 = (const double*)c->mmr_s64.p;
+    pos = (int32_t*)c->mmr_pos.p;
+    if (out_value64) {
+      if (int rc = ensure(c->mmr_v, nout * 8)) return rc;
+      val = (double*)c->mmr_v.p;
+    }
+  }
+  int32_t* flag = (int32_t*)c->mmr_flag.p;
+  MRAG_HIP(hipMemsetAsync(flag, 0, 4, s));
+  if (int rc = mrag_knn::mmr_select(mmr_args(ix, rows, s64, nq, m, k, lam, pos, val, flag), s)) return rc;
+  c->host_counters[2] = 0;
+  MRAG_HIP(hipMemcpyAsync(c->host_counters + 2, flag, 4, hipMemcpyDeviceToHost, s));
+  if (host) {
+    MRAG_HIP(hipMemcpyAsync(out_pos, pos, nout * 4, hipMemcpyDeviceToHost, s));
+    if (out_value64) MRAG_HIP(hipMemcpyAsync(out_value64, val, nout * 8, hipMemcpyDeviceToHost, s));
+  }
+  if (int rc = wait_stream(c, s)) return rc;
+  drain.armed = false;
+  MRAG_REQUIRE(c->host_counters[2] == 0, "cand_rows: a row id is not below the index size %lld", (long long)ix->n);
+  return MRAG_OK;
+}
+
+// The arguments mrag_knn_search_mmr and mrag_knn_mmr_select share, before any HIP call.
+int mmr_check(int32_t k, int32_t fetch_k, double lam, const char* fetch_name) {
+  MRAG_REQUIRE(fetch_k >= 1 && fetch_k <= MRAG_KNN_MMR_MAX_FETCH, "%s=%d unsupported (1..%d)", fetch_name, fetch_k,
+               MRAG_KNN_MMR_MAX_FETCH);
+  MRAG_REQUIRE(k >= 1 && k <= fetch_k, "k=%d unsupported (1..%s=%d)", k, fetch_name, fetch_k);
+  MRAG_REQUIRE(std::isfinite(lam) && lam >= 0.0 && lam <= 1.0, "lambda=%g is not in [0, 1]", lam);
   return MRAG_OK;
 }
 
@@ -2766,6 +2943,43 @@ int mrag_knn_search_labels(mrag_knn_index* ix, const float* queries, int64_t nq,
                    (long long)i);
   return search_entry(ix, queries, nq, k, MRAG_LABEL_ANY, label_filters, row_offset, out_scores, out_scores64,
                       out_rows, ptr_kind, stream_arg);
+}
+
+int mrag_knn_search_mmr(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k, int32_t fetch_k, double lambda,
+                        int32_t label_filter, const int32_t* label_filters, int64_t row_offset, float* out_scores,
+                        double* out_scores64, int64_t* out_rows, int32_t ptr_kind, void* stream_arg) {
+  if (int rc = mmr_check(k, fetch_k, lambda, "fetch_k")) return rc;
+  MRAG_REQUIRE(ix != nullptr, "index is NULL");
+  MRAG_REQUIRE(nq >= 0 && nq < (1 << 24), "nq=%lld out of range", (long long)nq);
+  MRAG_REQUIRE(ptr_kind == MRAG_PTR_HOST || ptr_kind == MRAG_PTR_DEVICE, "bad ptr_kind %d", ptr_kind);
+  if (nq == 0) return MRAG_OK;
+  MRAG_REQUIRE(queries != nullptr, "queries is NULL");
+  MRAG_REQUIRE(out_scores != nullptr, "out_scores is NULL");
+  MRAG_REQUIRE(out_rows != nullptr, "out_rows is NULL");
+  if (label_filters) {
+    if (ptr_kind == MRAG_PTR_HOST)  // as mrag_knn_search_labels
+      for (int64_t i = 0; i < nq; ++i)
+        MRAG_REQUIRE(label_filters[i] >= MRAG_LABEL_ANY, "label filter %d of query %lld invalid", label_filters[i],
+                     (long long)i);
+  } else {
+    MRAG_REQUIRE(label_filter >= MRAG_LABEL_ANY, "label filter %d invalid", label_filter);
+  }
+  return search_mmr_entry(ix, queries, nq, k, fetch_k, lambda, label_filters ? MRAG_LABEL_ANY : label_filter,
+                          label_filters, row_offset, out_scores, out_scores64, out_rows, ptr_kind, stream_arg);
+}
+
+int mrag_knn_mmr_select(mrag_knn_index* ix, const int64_t* cand_rows, const double* cand_scores64, int64_t nq,
+                        int32_t m, int32_t k, double lambda, int32_t* out_pos, double* out_value64, int32_t ptr_kind,
+                        void* stream_arg) {
+  if (int rc = mmr_check(k, m, lambda, "m")) return rc;
+  MRAG_REQUIRE(ix != nullptr, "index is NULL");
+  MRAG_REQUIRE(nq >= 0 && nq < (1 << 24), "nq=%lld out of range", (long long)nq);
+  MRAG_REQUIRE(ptr_kind == MRAG_PTR_HOST || ptr_kind == MRAG_PTR_DEVICE, "bad ptr_kind %d", ptr_kind);
+  if (nq == 0) return MRAG_OK;
+  MRAG_REQUIRE(cand_rows != nullptr, "cand_rows is NULL");
+  MRAG_REQUIRE(cand_scores64 != nullptr, "cand_scores64 is NULL");
+  MRAG_REQUIRE(out_pos != nullptr, "out_pos is NULL");
+  return mmr_select_entry(ix, cand_rows, cand_scores64, nq, m, k, lambda, out_pos, out_value64, ptr_kind, stream_arg);
 }
 
 #ifdef MRAG_K7_STAMPS
