@@ -191,7 +191,10 @@ def fuse_scores(text_scores, image_scores, final_n: Optional[int] = None):
     of queries, on the raw per-query hit scores the flat index returns.
 
     ``text_scores`` f32 [Q, kt], ``image_scores`` f32 [Q, ki] in hit order (score desc),
-    ``-inf`` marking missing hits (fewer matches than k). Each hit's score is first taken
+    ``-inf`` marking missing hits (fewer matches than k). Precondition shared with K12: the
+    finite scores of a list form its prefix (true of a descending list and of ``FlatIndex.search``'s
+    padding); this function masks and so tolerates other layouts, the kernel does not.
+    Each hit's score is first taken
     through the drop-in store's path (``1 - f32(1 - s)``, the f64 value a caller sees).
     Returns (``pick`` int64 [Q, final_n]: index into the concatenated text+image hit list,
     -1 past the end; ``combined`` f64 [Q, final_n]), ordered as the reference's stable

@@ -7,13 +7,16 @@
 // np.linalg.norm(axis=1) on f32 is sqrt(np.add.reduce(x*x, axis=1)); numpy's
 // add.reduce over a contiguous row is its pairwise summation (blocks of <=128
 // elements with 8 strided accumulators, halves split at n/2 rounded down to a
-// multiple of 8). Reproducing that order (and f32 rounding of every product and
+// multiple of 8; rows wider than its 8192-element buffer are summed block by
+// block). Reproducing that order (and f32 rounding of every product and
 // partial sum, no FMA contraction) makes this kernel's output bit-identical to
-// numpy's (checked by tests/test_knn_gpu.py::test_l2norm_bit_exact). Built with
-// -ffp-contract=off: hipcc otherwise fuses x*x + r into v_fmac_f32.
+// numpy's (checked by tests/test_l2norm_gpu.py: every width 1..1100, 2048, 4097, and
+// 20000 and 100003 for the block-by-block sum; in place; edge values). Built with -ffp-contract=off: hipcc otherwise fuses x*x + r into v_fmac_f32.
 //
-// Work is tiny (B rows x 512 after an encoder batch), so one thread owns a row;
-// the kernel is latency-bound by design and never on the critical path.
+// Work is tiny (B rows x 384 / 512 / 768 after an encoder batch, in place: y == x). One
+// wave owns a row while numpy's split has at most 8 leaves (dim <= 968; the encoder
+// widths get a compile-time leaf table), four rows per block; wider rows fall back to one
+// thread per row. The kernel is latency-bound by design and never on the critical path.
 #include "common.h"
 
 namespace {
@@ -42,7 +45,7 @@ __device__ float pw_leaf(const float* __restrict__ x, int n) {
 }
 
 // Iterative form of numpy's recursive pairwise_sum (depth <= 24).
-__device__ float pw_sumsq(const float* __restrict__ x, int n) {
+__device__ float pw_block_sumsq(const float* __restrict__ x, int n) {
   int off[24], len[24], st[24];
   float val[24];
   int fp = 0, vp = 0;
@@ -70,6 +73,15 @@ __device__ float pw_sumsq(const float* __restrict__ x, int n) {
     }
   }
   return val[0];
+}
+
+// numpy's add.reduce hands its inner loop at most `bufsize` (8192) elements at a time: the
+// pairwise sum is per such block, and the blocks' sums are added in order (one block: n <= 8192).
+constexpr int NP_BUFSIZE = 8192;
+__device__ float pw_sumsq(const float* __restrict__ x, int n) {
+  float tot = -0.0f;
+  for (int o = 0; o < n; o += NP_BUFSIZE) tot = __fadd_rn(tot, pw_block_sumsq(x + o, min(NP_BUFSIZE, n - o)));
+  return tot;
 }
 
 // numpy's recursion splits n > 128 at n2 = (n/2) - (n/2)%8, so for 128 < n <= 1024 the
