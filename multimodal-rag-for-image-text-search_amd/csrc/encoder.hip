@@ -18,35 +18,17 @@
 #include <vector>
 
 #include "common.h"
+#include "devbuf.h"
 #include "encoder_kernels.h"
 
 using namespace mrag_enc;
 
 namespace {
 
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-int buf_ensure(Buf& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return MRAG_OK;
-  if (b.p) MRAG_HIP(hipFree(b.p));
-  b.p = nullptr;
-  b.bytes = 0;
-  MRAG_HIP(hipMalloc(&b.p, std::max<size_t>(bytes, 256)));
-  b.bytes = std::max<size_t>(bytes, 256);
-  return MRAG_OK;
-}
-
-void buf_free(Buf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-}
+using mrag::DevBuf;  // weights, activations: freed with the handle (mrag_encoder_destroy)
 
 struct Layer {
-  Buf wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1g, ln1b, ln2g, ln2b;
+  DevBuf wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1g, ln1b, ln2g, ln2b;
 };
 
 __global__ void f32_to_f16_kernel(const float* __restrict__ in, _Float16* __restrict__ out, int64_t n) {
@@ -65,8 +47,8 @@ __global__ void f32_to_f16_kernel(const float* __restrict__ in, _Float16* __rest
 #define MRAG_IMG_LANE_MIN 128
 #endif
 struct Work {
-  Buf X, H16, QKV, ATT, F16, PATCH, IMG, IDS, MASK, TYPES, ROWS, POOL16, OUT, POOL32;
-  Buf XG, AG, HG, FG;  // the pooled rows of a CLIP tower's last layer (clip_layer_pooled)
+  DevBuf X, H16, QKV, ATT, F16, PATCH, IMG, IDS, MASK, TYPES, ROWS, POOL16, OUT, POOL32;
+  DevBuf XG, AG, HG, FG;  // the pooled rows of a CLIP tower's last layer (clip_layer_pooled)
   int64_t ws_tokens = 0, ws_batch = 0;
 };
 
@@ -77,9 +59,9 @@ struct mrag_encoder {
   hipStream_t stream = nullptr;
   std::vector<Layer> layers;
   // embeddings / heads
-  Buf patch_w, cls, pos, pre_g, pre_b, post_g, post_b, proj_w;  // vision
-  Buf tok, type0, emb_g, emb_b;                                  // text / bert (+pos); type0 = [2][D]
-  Buf pool_w, pool_b, cls_w, cls_b;                              // bert pair: pooler + classifier
+  DevBuf patch_w, cls, pos, pre_g, pre_b, post_g, post_b, proj_w;  // vision
+  DevBuf tok, type0, emb_g, emb_b;                                  // text / bert (+pos); type0 = [2][D]
+  DevBuf pool_w, pool_b, cls_w, cls_b;                              // bert pair: pooler + classifier
   std::map<std::string, bool> loaded;
   std::vector<std::string> expected;
   // workspace of a forward: w points at work[0], or at work[i] while image lane i is enqueued
@@ -123,50 +105,42 @@ bool sole_image_handle(const mrag_encoder* e) {
   return true;
 }
 
+// n host floats -> f16 at dst, through a temporary f32 copy on the device.
+int upload_f16(const float* host, int64_t n, _Float16* dst, hipStream_t s) {
+  DevBuf tmp;  // exactly these bytes (a fresh buffer); freed on return, after the wait below
+  if (int rc = mrag::ensure_doubling(tmp, (size_t)n * 4)) return rc;
+  hipError_t e = hipMemcpyAsync(tmp.p, host, (size_t)n * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)tmp.p, dst, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return mrag::fail(MRAG_ERR_HIP, "upload: %s", hipGetErrorString(e));
+  return MRAG_OK;
+}
+
 // Upload n floats from host to a device buffer as f32 or f16.
-int upload(Buf& b, const float* host, int64_t n, bool to_f16, hipStream_t s) {
+int upload(DevBuf& b, const float* host, int64_t n, bool to_f16, hipStream_t s) {
   if (!to_f16) {
-    if (int rc = buf_ensure(b, (size_t)n * 4)) return rc;
+    if (int rc = ensure(b, (size_t)n * 4)) return rc;
     MRAG_HIP(hipMemcpyAsync(b.p, host, (size_t)n * 4, hipMemcpyHostToDevice, s));
     return MRAG_OK;
   }
-  if (int rc = buf_ensure(b, (size_t)n * 2)) return rc;
-  void* tmp = nullptr;
-  MRAG_HIP(hipMalloc(&tmp, (size_t)n * 4));
-  hipError_t e = hipMemcpyAsync(tmp, host, (size_t)n * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)tmp,
-                       (_Float16*)b.p, n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(tmp);
-  if (e != hipSuccess) return mrag::fail(MRAG_ERR_HIP, "upload: %s", hipGetErrorString(e));
-  return MRAG_OK;
+  if (int rc = ensure(b, (size_t)n * 2)) return rc;
+  return upload_f16(host, n, (_Float16*)b.p, s);
 }
 
 // Copy into a slice [off, off+n) of an f16 buffer of `total` elements (fused QKV).
-int upload_slice_f16(Buf& b, int64_t total, int64_t off, const float* host, int64_t n, hipStream_t s) {
+int upload_slice_f16(DevBuf& b, int64_t total, int64_t off, const float* host, int64_t n, hipStream_t s) {
   if (!b.p) {
-    if (int rc = buf_ensure(b, (size_t)total * 2)) return rc;
+    if (int rc = ensure(b, (size_t)total * 2)) return rc;
   }
-  void* tmp = nullptr;
-  MRAG_HIP(hipMalloc(&tmp, (size_t)n * 4));
-  hipError_t e = hipMemcpyAsync(tmp, host, (size_t)n * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)tmp,
-                       (_Float16*)b.p + off, n);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(tmp);
-  if (e != hipSuccess) return mrag::fail(MRAG_ERR_HIP, "upload: %s", hipGetErrorString(e));
-  return MRAG_OK;
+  return upload_f16(host, n, (_Float16*)b.p + off, s);
 }
 
-int upload_slice_f32(Buf& b, int64_t total, int64_t off, const float* host, int64_t n, hipStream_t s) {
+int upload_slice_f32(DevBuf& b, int64_t total, int64_t off, const float* host, int64_t n, hipStream_t s) {
   if (!b.p) {
-    if (int rc = buf_ensure(b, (size_t)total * 4)) return rc;
+    if (int rc = ensure(b, (size_t)total * 4)) return rc;
   }
   MRAG_HIP(hipMemcpyAsync((float*)b.p + off, host, (size_t)n * 4, hipMemcpyHostToDevice, s));
   MRAG_HIP(hipStreamSynchronize(s));
@@ -272,26 +246,26 @@ int ensure_workspace(mrag_encoder* e, int B, int T) {
   // per-sequence buffers grow with B, per-token ones with B * T: either can grow alone (the
   // tokenisers pad to the longest sequence of a batch, so B can grow while B * T does not)
   if (B > e->w->ws_batch) {
-    if (int rc = buf_ensure(e->w->XG, (size_t)B * D * 4)) return rc;  // pooled rows of the last CLIP layer
-    if (int rc = buf_ensure(e->w->AG, (size_t)B * D * 2)) return rc;
-    if (int rc = buf_ensure(e->w->HG, (size_t)B * D * 2)) return rc;
-    if (int rc = buf_ensure(e->w->FG, (size_t)B * I * 2)) return rc;
-    if (int rc = buf_ensure(e->w->ROWS, (size_t)B * 4 + 256)) return rc;
-    if (int rc = buf_ensure(e->w->POOL16, (size_t)B * D * 2)) return rc;
+    if (int rc = ensure(e->w->XG, (size_t)B * D * 4)) return rc;  // pooled rows of the last CLIP layer
+    if (int rc = ensure(e->w->AG, (size_t)B * D * 2)) return rc;
+    if (int rc = ensure(e->w->HG, (size_t)B * D * 2)) return rc;
+    if (int rc = ensure(e->w->FG, (size_t)B * I * 2)) return rc;
+    if (int rc = ensure(e->w->ROWS, (size_t)B * 4 + 256)) return rc;
+    if (int rc = ensure(e->w->POOL16, (size_t)B * D * 2)) return rc;
     if (c.kind == MRAG_ENC_BERT_PAIR)
-      if (int rc = buf_ensure(e->w->POOL32, (size_t)B * D * 4)) return rc;
+      if (int rc = ensure(e->w->POOL32, (size_t)B * D * 4)) return rc;
     e->w->ws_batch = B;
   }
   if (tokens <= e->w->ws_tokens) return MRAG_OK;
-  if (int rc = buf_ensure(e->w->X, tokens * D * 4)) return rc;
-  if (int rc = buf_ensure(e->w->H16, tokens * D * 2)) return rc;
-  if (int rc = buf_ensure(e->w->QKV, tokens * 3 * D * 2)) return rc;
-  if (int rc = buf_ensure(e->w->ATT, tokens * D * 2)) return rc;
+  if (int rc = ensure(e->w->X, tokens * D * 4)) return rc;
+  if (int rc = ensure(e->w->H16, tokens * D * 2)) return rc;
+  if (int rc = ensure(e->w->QKV, tokens * 3 * D * 2)) return rc;
+  if (int rc = ensure(e->w->ATT, tokens * D * 2)) return rc;
   int64_t f16n = tokens * I;
   if (c.kind == MRAG_ENC_CLIP_VISION) f16n = std::max<int64_t>(f16n, tokens * vit_patch_kpad(c.patch_size));
-  if (int rc = buf_ensure(e->w->F16, f16n * 2)) return rc;
+  if (int rc = ensure(e->w->F16, f16n * 2)) return rc;
   if (c.kind == MRAG_ENC_CLIP_VISION) {
-    if (int rc = buf_ensure(e->w->PATCH, tokens * D * 4)) return rc;
+    if (int rc = ensure(e->w->PATCH, tokens * D * 4)) return rc;
   }
   e->w->ws_tokens = tokens;
   return MRAG_OK;
@@ -314,7 +288,7 @@ int gemm(const void* A, const void* W, const void* bias, void* C, int M, int N, 
   return launch_gemm(g, epi, s);
 }
 
-int layernorm(const float* x, const int* gather, float* y32, _Float16* y16, const Buf& g, const Buf& b, int rows,
+int layernorm(const float* x, const int* gather, float* y32, _Float16* y16, const DevBuf& g, const DevBuf& b, int rows,
               int D, float eps, hipStream_t s) {
   LayerNormArgs a{};
   a.x = x;
@@ -557,24 +531,14 @@ int mrag_encoder_destroy(mrag_encoder* e) {
     if (e->null_ev) (void)hipEventDestroy(e->null_ev);
     for (auto& kv : e->graphs) (void)hipGraphExecDestroy(kv.second.exec);
     e->graphs.clear();
-    for (auto& L : e->layers)
-      for (Buf* b : {&L.wqkv, &L.bqkv, &L.wo, &L.bo, &L.w1, &L.b1, &L.w2, &L.b2, &L.ln1g, &L.ln1b, &L.ln2g, &L.ln2b})
-        buf_free(*b);
-    for (Buf* b : {&e->patch_w, &e->cls, &e->pos, &e->pre_g, &e->pre_b, &e->post_g, &e->post_b, &e->proj_w, &e->tok,
-                   &e->type0, &e->emb_g, &e->emb_b, &e->pool_w, &e->pool_b, &e->cls_w, &e->cls_b})
-      buf_free(*b);
-    for (Work& w : e->work)
-      for (Buf* b : {&w.X, &w.H16, &w.QKV, &w.ATT, &w.F16, &w.PATCH, &w.IMG, &w.IDS, &w.MASK, &w.ROWS, &w.POOL16, &w.OUT,
-                     &w.POOL32, &w.TYPES, &w.XG, &w.AG, &w.HG, &w.FG})
-        buf_free(*b);
     for (int i = 0; i < MRAG_IMG_LANES; ++i) {
       if (e->lane_stream[i]) (void)hipStreamDestroy(e->lane_stream[i]);
       if (e->lane_ev[i]) (void)hipEventDestroy(e->lane_ev[i]);
     }
     if (e->lane_fork) (void)hipEventDestroy(e->lane_fork);
     (void)hipStreamDestroy(e->stream);
+    delete e;  // on the handle's device, its streams drained above: the buffers free themselves
   }
-  delete e;
   return MRAG_OK;
 }
 
@@ -759,13 +723,13 @@ int mrag_encoder_embed_images(mrag_encoder* e, const uint8_t* images, int32_t ba
   e->w = &e->work[0];
   const uint8_t* img = images;
   if (ptr_kind == MRAG_PTR_HOST) {
-    if (int rc = buf_ensure(e->w->IMG, (size_t)B * S * S * 3)) return rc;
+    if (int rc = ensure(e->w->IMG, (size_t)B * S * S * 3)) return rc;
     MRAG_HIP(hipMemcpyAsync(e->w->IMG.p, images, (size_t)B * S * S * 3, hipMemcpyHostToDevice, s));
     img = (const uint8_t*)e->w->IMG.p;
   }
   float* dst = out;
   if (ptr_kind == MRAG_PTR_HOST) {
-    if (int rc = buf_ensure(e->w->OUT, (size_t)B * c.proj_dim * 4)) return rc;
+    if (int rc = ensure(e->w->OUT, (size_t)B * c.proj_dim * 4)) return rc;
     dst = (float*)e->w->OUT.p;
   }
   if (lanes > 1) MRAG_HIP(hipEventRecord(e->lane_fork, s));  // fork
@@ -813,11 +777,11 @@ int mrag_encoder_embed_tokens(mrag_encoder* e, const int32_t* ids, const int32_t
   const int32_t* dids = ids;
   const int32_t* dmask = mask;
   if (ptr_kind == MRAG_PTR_HOST) {
-    if (int rc = buf_ensure(e->w->IDS, (size_t)B * T * 4)) return rc;
+    if (int rc = ensure(e->w->IDS, (size_t)B * T * 4)) return rc;
     MRAG_HIP(hipMemcpyAsync(e->w->IDS.p, ids, (size_t)B * T * 4, hipMemcpyHostToDevice, s));
     dids = (const int32_t*)e->w->IDS.p;
     if (mask) {
-      if (int rc = buf_ensure(e->w->MASK, (size_t)B * T * 4)) return rc;
+      if (int rc = ensure(e->w->MASK, (size_t)B * T * 4)) return rc;
       MRAG_HIP(hipMemcpyAsync(e->w->MASK.p, mask, (size_t)B * T * 4, hipMemcpyHostToDevice, s));
       dmask = (const int32_t*)e->w->MASK.p;
     }
@@ -827,7 +791,7 @@ int mrag_encoder_embed_tokens(mrag_encoder* e, const int32_t* ids, const int32_t
   const int outD = c.kind == MRAG_ENC_BERT ? D : c.proj_dim;
   float* dst = out;
   if (ptr_kind == MRAG_PTR_HOST) {
-    if (int rc = buf_ensure(e->w->OUT, (size_t)B * outD * 4)) return rc;
+    if (int rc = ensure(e->w->OUT, (size_t)B * outD * 4)) return rc;
     dst = (float*)e->w->OUT.p;
   }
   auto forward = [&](hipStream_t s) -> int {
@@ -899,16 +863,16 @@ int mrag_encoder_score_pairs(mrag_encoder* e, const int32_t* ids, const int32_t*
   const int32_t* dmask = mask;
   const int32_t* dtypes = type_ids;
   if (ptr_kind == MRAG_PTR_HOST) {
-    if (int rc = buf_ensure(e->w->IDS, (size_t)B * T * 4)) return rc;
+    if (int rc = ensure(e->w->IDS, (size_t)B * T * 4)) return rc;
     MRAG_HIP(hipMemcpyAsync(e->w->IDS.p, ids, (size_t)B * T * 4, hipMemcpyHostToDevice, s));
     dids = (const int32_t*)e->w->IDS.p;
     if (mask) {
-      if (int rc = buf_ensure(e->w->MASK, (size_t)B * T * 4)) return rc;
+      if (int rc = ensure(e->w->MASK, (size_t)B * T * 4)) return rc;
       MRAG_HIP(hipMemcpyAsync(e->w->MASK.p, mask, (size_t)B * T * 4, hipMemcpyHostToDevice, s));
       dmask = (const int32_t*)e->w->MASK.p;
     }
     if (type_ids) {
-      if (int rc = buf_ensure(e->w->TYPES, (size_t)B * T * 4)) return rc;
+      if (int rc = ensure(e->w->TYPES, (size_t)B * T * 4)) return rc;
       MRAG_HIP(hipMemcpyAsync(e->w->TYPES.p, type_ids, (size_t)B * T * 4, hipMemcpyHostToDevice, s));
       dtypes = (const int32_t*)e->w->TYPES.p;
     }
@@ -936,7 +900,7 @@ int mrag_encoder_score_pairs(mrag_encoder* e, const int32_t* ids, const int32_t*
   if (int rc = launch_gemm(pg, EPI_F32, s)) return rc;
   float* dst = out;
   if (ptr_kind == MRAG_PTR_HOST) {
-    if (int rc = buf_ensure(e->w->OUT, (size_t)B * NL * 4)) return rc;
+    if (int rc = ensure(e->w->OUT, (size_t)B * NL * 4)) return rc;
     dst = (float*)e->w->OUT.p;
   }
   if (int rc = launch_cls_head((const float*)e->w->POOL32.p, (const float*)e->cls_w.p, (const float*)e->cls_b.p, dst, B, D,

@@ -8,19 +8,18 @@
 // Pillow (or raises the reference's exception for them), so the result is the same as the
 // per-file path's.
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include <sys/stat.h>
 
 #include "common.h"
+#include "host_threads.h"
 #include "jpeg_parse.h"
 #include "png_parse.h"
 #include "staged.h"
@@ -171,25 +170,6 @@ void stage(mrag_files& F, int i) {
   }
 }
 
-template <class Fn>
-bool on_threads(int n, int threads, Fn fn) {
-  const int nth = std::max(1, std::min<int>(threads > 0 ? threads : 1, n));
-  std::atomic<int> next{0};
-  std::atomic<bool> thrown{false};
-  auto work = [&]() {
-    try {
-      for (int i = next++; i < n; i = next++) fn(i);
-    } catch (...) {
-      thrown = true;
-    }
-  };
-  std::vector<std::thread> th;
-  for (int t = 1; t < nth; ++t) th.emplace_back(work);
-  work();
-  for (auto& x : th) x.join();
-  return !thrown;
-}
-
 int prepare_impl(const char* const* paths, int32_t n, int32_t threads, int32_t device_decode, int64_t max_pixels,
                  mrag_files** out) {
   if (!out || n < 0 || (n > 0 && !paths)) return mrag::fail(MRAG_ERR_ARG, "NULL argument");
@@ -209,7 +189,7 @@ int prepare_impl(const char* const* paths, int32_t n, int32_t threads, int32_t d
   F->pp.resize((size_t)n);
   F->off.assign((size_t)n, 0);
   F->seg0.assign((size_t)n, 0);
-  if (!on_threads(n, threads, [&](int i) { classify(*F, i, paths[i], device_decode != 0, max_pixels); })) return fail_oom();
+  if (!mrag::for_each_index(n, threads, [&](int i) { classify(*F, i, paths[i], device_decode != 0, max_pixels); })) return fail_oom();
   // the arena: every JPEG's segments (K13's stage layout, file order), then every PNG's scanlines
   int64_t pos = 0;
   int32_t nseg = 0;
@@ -228,7 +208,7 @@ int prepare_impl(const char* const* paths, int32_t n, int32_t threads, int32_t d
     }
   F->nbits.assign((size_t)nseg, 0);
   if (pos > 0) F->arena = arena_get((size_t)pos);
-  if (!on_threads(n, threads, [&](int i) { stage(*F, i); })) return fail_oom();
+  if (!mrag::for_each_index(n, threads, [&](int i) { stage(*F, i); })) return fail_oom();
   for (int i = 0; i < n; ++i) {  // the parses of files K13 / K14 do not take are not needed again
     if (F->kind[i] != 1) std::vector<mrag_jpeg::Segment>().swap(F->jp[i].segs);
     if (F->kind[i] != 2) std::vector<std::pair<int64_t, int64_t>>().swap(F->pp[i].idat);
@@ -318,7 +298,7 @@ int mrag_files_free(mrag_files* F) {
 int mrag_paths_exist(const char* const* paths, int32_t n, int32_t threads, int32_t* out) {
   MRAG_REQUIRE(n >= 0 && (n == 0 || (paths && out)), "NULL argument");
   try {
-    on_threads(n, threads, [&](int i) {
+    (void)mrag::for_each_index(n, threads, [&](int i) {  // the body does not throw
       const char* p = paths[i] && paths[i][0] ? paths[i] : ".";
       struct stat st;
       if (stat(p, &st) == 0) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devbuf.h"
 
 namespace {
 
@@ -182,14 +183,14 @@ TapTable taps(int in_size, int out_size, int o0, int cnt) {
   return t;
 }
 
-// grow-only device workspace (per process; calls are serialised by `mu`)
+// grow-only device workspace (per process; calls are serialised by `mu`), made again when the
+// calling thread's device is another
 struct Workspace {
   std::mutex mu;
-  void* p = nullptr;
-  size_t cap = 0;
+  mrag::DevBuf buf;
   int dev = -1;
 };
-Workspace g_ws;
+Workspace& g_ws = *new Workspace;  // never deleted: no hipFree at process exit, when the HIP runtime may be gone
 
 }  // namespace
 
@@ -263,15 +264,10 @@ extern "C" int mrag_image_resize_crop(const uint8_t* pixels, const int64_t* offs
   const size_t coef_off = (plan_bytes + 255) / 256 * 256;
   const size_t tmp_off = coef_off + (coef.size() * 4 + 255) / 256 * 256;
   const size_t need = tmp_off + (size_t)tmp_bytes;
-  if (need > g_ws.cap || dev != g_ws.dev) {
-    if (g_ws.p) (void)hipFree(g_ws.p);
-    g_ws.p = nullptr;
-    g_ws.cap = 0;
-    MRAG_HIP(hipMalloc(&g_ws.p, need));
-    g_ws.cap = need;
-    g_ws.dev = dev;
-  }
-  char* ws = (char*)g_ws.p;
+  if (dev != g_ws.dev) g_ws.buf.reset();
+  if (int rc = mrag::ensure(g_ws.buf, need)) return rc;  // need >= 256: exactly `need` bytes
+  g_ws.dev = dev;
+  char* ws = (char*)g_ws.buf.p;
   MRAG_HIP(hipMemcpyAsync(ws, plans.data(), plan_bytes, hipMemcpyHostToDevice, s));
   MRAG_HIP(hipMemcpyAsync(ws + coef_off, coef.data(), coef.size() * 4, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)((max_rows + RH_ROWS - 1) / RH_ROWS), (unsigned)n), dim3(256), 0, s, pixels,

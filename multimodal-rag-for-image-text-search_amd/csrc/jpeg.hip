@@ -19,13 +19,14 @@
 // Files K13 does not support (progressive, arithmetic, CMYK, 4:4:0, tiny chroma) are reported by
 // mrag_jpeg_probe and decoded on the host by the caller, as the reference decodes everything.
 #include <algorithm>
-#include <atomic>
 #include <cstring>
 #include <mutex>
 #include <thread>
 #include <vector>
 
 #include "common.h"
+#include "devbuf.h"
+#include "host_threads.h"
 #include "jpeg_parse.h"
 #include "staged.h"
 
@@ -160,29 +161,13 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const Image* __restrict
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-int ensure(DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return MRAG_OK;
-  const size_t c = std::max(bytes, b.cap * 2);
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  MRAG_HIP(hipMalloc(&b.p, c));
-  b.cap = c;
-  return MRAG_OK;
-}
-
 // Per-device scratch, grown on demand and reused by every batch (calls serialise on its lock).
 struct Ctx {
   std::mutex mu;
-  DevBuf ecs, imgs, segs, coef, planes;
-  uint8_t* stage = nullptr;  // pinned host staging of the entropy-coded bytes
-  size_t stage_cap = 0;
+  mrag::DevBuf ecs, imgs, segs, coef, planes;
+  mrag::PinnedBuf stage;  // host staging of the entropy-coded bytes
 };
-Ctx g_ctx[64];
+Ctx* const g_ctx = new Ctx[64];  // never deleted: no hipFree at process exit, when the HIP runtime may be gone
 
 }  // namespace
 
@@ -218,20 +203,6 @@ static int jpeg_decode_impl(const uint8_t* const* files, const int64_t* sizes, i
 
   // host threads over the files: parse, then (below) unstuff into the pinned stage
   const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({8, (int64_t)std::thread::hardware_concurrency(), (n + 15) / 16}));
-  std::atomic<bool> thrown{false};  // an exception (allocation) on a host thread: reported, not std::terminate
-  auto parallel = [&](auto fn) {
-    auto part = [&](int w) {
-      try {
-        for (int i = w; i < n; i += nth) fn(i);
-      } catch (...) {
-        thrown = true;
-      }
-    };
-    std::vector<std::thread> th;
-    for (int w = 1; w < nth; ++w) th.emplace_back(part, w);
-    part(0);
-    for (auto& x : th) x.join();
-  };
   std::vector<Parsed> Pv;
   std::vector<const Parsed*> P((size_t)n);
   std::vector<char> ok((size_t)n, 1);
@@ -239,8 +210,9 @@ static int jpeg_decode_impl(const uint8_t* const* files, const int64_t* sizes, i
     for (int i = 0; i < n; ++i) P[i] = st->P[i];
   } else {
     Pv.resize((size_t)n);
-    parallel([&](int i) { ok[i] = parse(files[i], sizes[i], Pv[i]) ? 1 : 0; });
-    if (thrown) return mrag::fail(MRAG_ERR_OOM, "jpeg: host allocation failed while parsing");
+    // an exception (allocation) on a host thread is reported, not std::terminate
+    if (!mrag::for_each_index(n, nth, [&](int i) { ok[i] = parse(files[i], sizes[i], Pv[i]) ? 1 : 0; }))
+      return mrag::fail(MRAG_ERR_OOM, "jpeg: host allocation failed while parsing");
     for (int i = 0; i < n; ++i) P[i] = &Pv[i];
   }
   std::vector<Image> imgs((size_t)n);
@@ -273,40 +245,35 @@ static int jpeg_decode_impl(const uint8_t* const* files, const int64_t* sizes, i
     max_blocks = std::max(max_blocks, P[i]->coef_blocks);
     max_quads = std::max(max_quads, (int64_t)(im.width + 3) / 4 * im.height);
   }
-  const uint8_t* src = C.stage;
+  const uint8_t* src = C.stage.p;
   if (st) {
     MRAG_REQUIRE(st->bytes == stage_bytes, "jpeg: staged %lld bytes, the layout needs %lld", (long long)st->bytes,
                  (long long)stage_bytes);
     for (size_t q = 0; q < segs.size(); ++q) segs[q].nbits = st->nbits[q];
     src = st->stage;
-  } else if (stage_bytes > (int64_t)C.stage_cap) {
-    const size_t cap = std::max<size_t>((size_t)stage_bytes, C.stage_cap * 2);
+  } else if (stage_bytes > (int64_t)C.stage.bytes) {
     if (int rc = mrag::blocking_wait(s)) return rc;  // a previous batch's copy may still read the old buffer
-    if (C.stage) (void)hipHostFree(C.stage);
-    C.stage = nullptr;
-    C.stage_cap = 0;
-    MRAG_HIP(hipHostMalloc((void**)&C.stage, cap, hipHostMallocDefault));
-    C.stage_cap = cap;
+    if (int rc = mrag::ensure_doubling(C.stage, (size_t)stage_bytes)) return rc;
   }
   if (!st) {
     // the previous batch's copy out of the staging buffer must be done before it is rewritten
     if (int rc = mrag::blocking_wait(s)) return rc;
-    src = C.stage;
-    parallel([&](int i) {
+    src = C.stage.p;
+    const bool staged = mrag::for_each_index(n, nth, [&](int i) {
       for (int q = imgs[i].seg0, e = imgs[i].seg0 + (int)P[i]->segs.size(); q < e; ++q) {
-        uint8_t* dst = C.stage + segs[q].uoff;
+        uint8_t* dst = C.stage.p + segs[q].uoff;
         const int64_t u = unstuff(files[i] + seg_src[q], seg_len[q], dst);
         std::memset(dst + u, 0, (size_t)((u + 15) / 16 * 16 - u));
         segs[q].nbits = (uint32_t)(u * 8);
       }
     });
-    if (thrown) return mrag::fail(MRAG_ERR_OOM, "jpeg: host allocation failed while staging");
+    if (!staged) return mrag::fail(MRAG_ERR_OOM, "jpeg: host allocation failed while staging");
   }
-  if (int rc = ensure(C.ecs, (size_t)stage_bytes)) return rc;
-  if (int rc = ensure(C.imgs, sizeof(Image) * (size_t)n)) return rc;
-  if (int rc = ensure(C.segs, sizeof(ParSeg) * segs.size())) return rc;
-  if (int rc = ensure(C.coef, (size_t)blocks * 128)) return rc;
-  if (int rc = ensure(C.planes, (size_t)planes)) return rc;
+  if (int rc = mrag::ensure_doubling(C.ecs, (size_t)stage_bytes)) return rc;
+  if (int rc = mrag::ensure_doubling(C.imgs, sizeof(Image) * (size_t)n)) return rc;
+  if (int rc = mrag::ensure_doubling(C.segs, sizeof(ParSeg) * segs.size())) return rc;
+  if (int rc = mrag::ensure_doubling(C.coef, (size_t)blocks * 128)) return rc;
+  if (int rc = mrag::ensure_doubling(C.planes, (size_t)planes)) return rc;
   // an error return from here on first drains s: the copies read imgs / segs on this stack frame
   // and the staging arena, which the caller may hand back to its pool
   mrag::StreamDrain drain(s);

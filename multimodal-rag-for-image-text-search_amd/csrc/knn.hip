@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devbuf.h"
 #include "knn_compact.h"
 #include "knn_generic.h"
 #include "knn_mmr.h"
@@ -1828,40 +1829,7 @@ __global__ void fill_empty_kernel(float* s, double* s64, int64_t* r, int64_t n) 
 // ---------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------
-// A device allocation owned by its holder: move-only, freed when the holder is destroyed (which
-// must happen with the allocation's device current: see mrag_knn_destroy).
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) {
-      if (p) (void)hipFree(p);
-      p = std::exchange(o.p, nullptr);
-      bytes = std::exchange(o.bytes, 0);
-    }
-    return *this;
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-int ensure(DevBuf& b, size_t bytes) {
-  if (b.bytes >= bytes && b.p) return MRAG_OK;
-  if (b.p) {
-    MRAG_HIP(hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  const size_t want = std::max<size_t>(bytes, 256);
-  MRAG_HIP(hipMalloc(&b.p, want));
-  b.bytes = want;
-  return MRAG_OK;
-}
+using mrag::DevBuf;  // devbuf.h; ensure() is found through it
 
 // Kernel instances for a plan's fields (knn_plan.h decides; these only look up).
 typedef void (*scan_fn)(ScanParams);
@@ -1957,10 +1925,9 @@ struct SearchCtx {
   hipEvent_t done = nullptr;         // end of the search's device work (waited by spinning)
   hipEvent_t null_ev = nullptr;      // device inputs on the NULL stream: the search waits for it
   hipEvent_t ev0 = nullptr, ev1 = nullptr;  // scan timing (mrag_knn_profile)
-  mrag_knn::Workspace gws[8];               // K7g buffers
+  DevBuf gws[8];                            // K7g buffers
   // on the index's device (ctx_get, ~mrag_knn_index); the DevBufs free themselves
   ~SearchCtx() {
-    mrag_knn::release(gws);
     if (host_counters) (void)hipHostFree(host_counters);
     if (host_fail) (void)hipHostFree(host_fail);
     for (hipEvent_t e : {done, null_ev, ev0, ev1})
@@ -2046,41 +2013,66 @@ int ctx_get(mrag_knn_index* ix, SearchCtx** out) {
 
 struct CtxLease {
   mrag_knn_index* ix;
-  SearchCtx* c;
+  SearchCtx* c;  // null: nothing leased yet
   ~CtxLease() {
+    if (!c) return;
     std::lock_guard<std::mutex> lk(ix->pool_mu);
     ix->ctx_free.push_back(c);
   }
 };
 
+// New corpus buffers for `rows` rows, in place of the index's, which they replace once their rows
+// are copied in: the capacity (a multiple of the 64- and 48-row scan tiles and of K7g's
+// 128-column GEMM tile), then on ix->stream the rows from first_unused_row on zeroed and labelled
+// deleted. An error return frees what was allocated so far.
+struct Corpus {
+  DevBuf x16, x32, xn, labels;
+  int64_t cap = 0;
+};
+
+int alloc_corpus(mrag_knn_index* ix, int64_t rows, int64_t first_unused_row, Corpus& c) {
+  const int DP = ix->DP;
+  const int64_t ncap = (rows + 767) / 768 * 768;
+  if (int rc = ensure(c.x16, (size_t)ncap * DP * 2)) return rc;
+  if (int rc = ensure(c.x32, (size_t)ncap * DP * 4)) return rc;
+  if (int rc = ensure(c.xn, (size_t)ncap * 8)) return rc;
+  if (int rc = ensure(c.labels, (size_t)ncap * 4)) return rc;
+  c.cap = ncap;
+  hipStream_t s = ix->stream;
+  const int64_t first = first_unused_row, tail = ncap - first;
+  if (tail > 0) {
+    MRAG_HIP(hipMemsetAsync((_Float16*)c.x16.p + first * DP, 0, (size_t)tail * DP * 2, s));
+    MRAG_HIP(hipMemsetAsync((float*)c.x32.p + first * DP, 0, (size_t)tail * DP * 4, s));
+    MRAG_HIP(hipMemsetAsync((double*)c.xn.p + first, 0, (size_t)tail * 8, s));
+    hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)((tail + 255) / 256)), dim3(256), 0, s,
+                       (int32_t*)c.labels.p + first, tail, (int32_t)MRAG_LABEL_DELETED);
+    MRAG_CHECK_LAUNCH();
+  }
+  return MRAG_OK;
+}
+
+// The index takes the new buffers (its old ones are freed) once nothing queued reads either.
+void adopt_corpus(mrag_knn_index* ix, Corpus& c) {
+  ix->x16 = std::move(c.x16);
+  ix->x32 = std::move(c.x32);
+  ix->xn = std::move(c.xn);
+  ix->labels = std::move(c.labels);
+  ix->cap = c.cap;
+}
+
 int grow(mrag_knn_index* ix, int64_t need) {
   if (need <= ix->cap) return MRAG_OK;
-  int64_t ncap = std::max<int64_t>({(int64_t)TILE_ROWS, ix->cap * 2, need});
-  ncap = (ncap + 767) / 768 * 768;  // a multiple of the 64- and 48-row scan tiles and of K7g's 128-column GEMM tile
-  DevBuf nx16, nx32, nxn, nlab;  // an error return frees what was allocated so far
-  if (int rc = ensure(nx16, (size_t)ncap * ix->DP * 2)) return rc;
-  if (int rc = ensure(nx32, (size_t)ncap * ix->DP * 4)) return rc;
-  if (int rc = ensure(nxn, (size_t)ncap * 8)) return rc;
-  if (int rc = ensure(nlab, (size_t)ncap * 4)) return rc;
+  Corpus c;
+  if (int rc = alloc_corpus(ix, std::max<int64_t>({(int64_t)TILE_ROWS, ix->cap * 2, need}), 0, c)) return rc;
   hipStream_t s = ix->stream;
-  MRAG_HIP(hipMemsetAsync(nx16.p, 0, (size_t)ncap * ix->DP * 2, s));
-  MRAG_HIP(hipMemsetAsync(nx32.p, 0, (size_t)ncap * ix->DP * 4, s));
-  MRAG_HIP(hipMemsetAsync(nxn.p, 0, (size_t)ncap * 8, s));
-  hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)((ncap + 255) / 256)), dim3(256), 0, s,
-                     (int32_t*)nlab.p, ncap, (int32_t)MRAG_LABEL_DELETED);
-  MRAG_CHECK_LAUNCH();
   if (ix->n > 0) {
-    MRAG_HIP(hipMemcpyAsync(nx16.p, ix->x16.p, (size_t)ix->n * ix->DP * 2, hipMemcpyDeviceToDevice, s));
-    MRAG_HIP(hipMemcpyAsync(nx32.p, ix->x32.p, (size_t)ix->n * ix->DP * 4, hipMemcpyDeviceToDevice, s));
-    MRAG_HIP(hipMemcpyAsync(nxn.p, ix->xn.p, (size_t)ix->n * 8, hipMemcpyDeviceToDevice, s));
-    MRAG_HIP(hipMemcpyAsync(nlab.p, ix->labels.p, (size_t)ix->n * 4, hipMemcpyDeviceToDevice, s));
+    MRAG_HIP(hipMemcpyAsync(c.x16.p, ix->x16.p, (size_t)ix->n * ix->DP * 2, hipMemcpyDeviceToDevice, s));
+    MRAG_HIP(hipMemcpyAsync(c.x32.p, ix->x32.p, (size_t)ix->n * ix->DP * 4, hipMemcpyDeviceToDevice, s));
+    MRAG_HIP(hipMemcpyAsync(c.xn.p, ix->xn.p, (size_t)ix->n * 8, hipMemcpyDeviceToDevice, s));
+    MRAG_HIP(hipMemcpyAsync(c.labels.p, ix->labels.p, (size_t)ix->n * 4, hipMemcpyDeviceToDevice, s));
   }
   MRAG_HIP(hipStreamSynchronize(s));
-  ix->x16 = std::move(nx16);  // frees the old buffers
-  ix->x32 = std::move(nx32);
-  ix->xn = std::move(nxn);
-  ix->labels = std::move(nlab);
-  ix->cap = ncap;
+  adopt_corpus(ix, c);
   return MRAG_OK;
 }
 
@@ -2121,23 +2113,9 @@ int compact_rows(mrag_knn_index* ix, int64_t* remap_out, int64_t* new_size) {
   ix->compact_bytes[0] = n * 12;  // the labels twice, the remap once
   if (live < n) {
     const int DP = ix->DP;
-    int64_t ncap = std::max<int64_t>((int64_t)TILE_ROWS, live);
-    ncap = (ncap + 767) / 768 * 768;  // grow()'s rule
-    DevBuf nx16, nx32, nxn, nlab;     // an error return frees what was allocated so far
-    if (int rc = ensure(nx16, (size_t)ncap * DP * 2)) return rc;
-    if (int rc = ensure(nx32, (size_t)ncap * DP * 4)) return rc;
-    if (int rc = ensure(nxn, (size_t)ncap * 8)) return rc;
-    if (int rc = ensure(nlab, (size_t)ncap * 4)) return rc;
+    Corpus c;
     mrag::StreamDrain drain(s);  // nothing queued may outlive the new buffers on an error return
-    const int64_t tail = ncap - live;  // zeroed and labelled deleted, as grow() leaves it
-    if (tail > 0) {
-      MRAG_HIP(hipMemsetAsync((_Float16*)nx16.p + live * DP, 0, (size_t)tail * DP * 2, s));
-      MRAG_HIP(hipMemsetAsync((float*)nx32.p + live * DP, 0, (size_t)tail * DP * 4, s));
-      MRAG_HIP(hipMemsetAsync((double*)nxn.p + live, 0, (size_t)tail * 8, s));
-      hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)((tail + 255) / 256)), dim3(256), 0, s,
-                         (int32_t*)nlab.p + live, tail, (int32_t)MRAG_LABEL_DELETED);
-      MRAG_CHECK_LAUNCH();
-    }
+    if (int rc = alloc_corpus(ix, std::max<int64_t>((int64_t)TILE_ROWS, live), live, c)) return rc;
     mrag_knn::GatherRows g;
     g.x16 = (const _Float16*)ix->x16.p;
     g.x32 = (const float*)ix->x32.p;
@@ -2146,10 +2124,10 @@ int compact_rows(mrag_knn_index* ix, int64_t* remap_out, int64_t* new_size) {
     g.remap = (const int32_t*)ix->remap.p;
     g.n = n;
     g.DP = DP;
-    g.out_x16 = (_Float16*)nx16.p;
-    g.out_x32 = (float*)nx32.p;
-    g.out_xn = (double*)nxn.p;
-    g.out_labels = (int32_t*)nlab.p;
+    g.out_x16 = (_Float16*)c.x16.p;
+    g.out_x32 = (float*)c.x32.p;
+    g.out_xn = (double*)c.xn.p;
+    g.out_labels = (int32_t*)c.labels.p;
     MRAG_HIP(hipEventRecord(ix->cev[1], s));
     if (int rc = mrag_knn::gather_rows(g, s)) return rc;
     MRAG_HIP(hipEventRecord(ix->cev[2], s));
@@ -2158,11 +2136,7 @@ int compact_rows(mrag_knn_index* ix, int64_t* remap_out, int64_t* new_size) {
     MRAG_HIP(hipEventElapsedTime(&ms, ix->cev[1], ix->cev[2]));
     ix->compact_ms[1] = ms;
     ix->compact_bytes[1] = 2 * live * ((int64_t)DP * 6 + 12) + n * 4;
-    ix->x16 = std::move(nx16);  // frees the old buffers
-    ix->x32 = std::move(nx32);
-    ix->xn = std::move(nxn);
-    ix->labels = std::move(nlab);
-    ix->cap = ncap;
+    adopt_corpus(ix, c);
     ix->n = live;
   } else {
     ix->compact_ms[1] = 0.0;
@@ -2531,36 +2505,55 @@ void publish_stats(mrag_knn_index* ix, SearchCtx* c, const SearchStats& st) {
   std::copy(st.info, st.info + 8, ix->last_info);
 }
 
-// mrag_knn_search (label_filters null: label_filter for every query) and mrag_knn_search_labels.
-int search_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k, int32_t label_filter,
-                 const int32_t* label_filters, int64_t row_offset, float* out_scores, double* out_scores64,
-                 int64_t* out_rows, int32_t ptr_kind, void* stream_arg) {
-  std::shared_lock<std::shared_mutex> rl(ix->rw);
-  mrag::DeviceGuard g(ix->device);
-  if (nq == 0) return MRAG_OK;
+// What every call that runs on a search context holds, in the order it is taken: the index's
+// shared lock, its device, a leased context, the stream, and (host pointers) the context's
+// device-side output buffers. The members are destroyed in reverse: the drain before the lease
+// before the shared lock, so an error after the first launch drains s before the context returns
+// to the pool and mutations may free the corpus buffers.
+struct SearchCall {
+  mrag_knn_index* ix;
+  std::shared_lock<std::shared_mutex> rl;
+  mrag::DeviceGuard g;
+  CtxLease lease;
+  mrag::StreamDrain drain;  // armed by open()
   SearchCtx* c = nullptr;
-  if (int rc = ctx_get(ix, &c)) return rc;
-  CtxLease lease{ix, c};
-  bool profile;
-  {
-    std::lock_guard<std::mutex> lk(ix->pool_mu);
-    profile = ix->profile;
-  }
-  MRAG_REQUIRE(queries && out_scores && out_rows, "NULL query/output pointer");
-  hipStream_t s = stream_arg ? (hipStream_t)stream_arg : ix->stream;
-  const bool host = ptr_kind == MRAG_PTR_HOST;
-  if (!host && !stream_arg)
-    if (int rc = mrag::wait_null_stream(c->null_ev, s)) return rc;
-  // destroyed before the lease and the shared lock: an error after the first launch drains s
-  // before the context returns to the pool and mutations may free the corpus buffers
-  mrag::StreamDrain drain(s);
-  const int64_t nout = nq * k;
+  hipStream_t s = nullptr;
+  bool host = false, profile = false;
+  // a search's outputs: the caller's, and where the kernels write them (the same for device pointers)
+  int64_t nout = 0;
+  float *out_scores = nullptr, *os = nullptr;
+  double *out_scores64 = nullptr, *os64 = nullptr;
+  int64_t *out_rows = nullptr, *orr = nullptr;
 
-  // output destinations (device)
-  float* os = out_scores;
-  double* os64 = out_scores64;
-  int64_t* orr = out_rows;
-  if (host) {
+  explicit SearchCall(mrag_knn_index* index)
+      : ix(index), rl(index->rw), g(index->device), lease{index, nullptr}, drain(nullptr) {
+    drain.armed = false;
+  }
+
+  // the context, the stream (device pointers with no stream of the caller's: after the null stream)
+  int open(int32_t ptr_kind, void* stream_arg) {
+    if (int rc = ctx_get(ix, &c)) return rc;
+    lease.c = c;
+    {
+      std::lock_guard<std::mutex> lk(ix->pool_mu);
+      profile = ix->profile;
+    }
+    s = stream_arg ? (hipStream_t)stream_arg : ix->stream;
+    host = ptr_kind == MRAG_PTR_HOST;
+    if (!host && !stream_arg)
+      if (int rc = mrag::wait_null_stream(c->null_ev, s)) return rc;
+    drain.s = s;
+    drain.armed = true;
+    return MRAG_OK;
+  }
+
+  // output destinations (device) of n results per array
+  int outputs(int64_t n, float* scores, double* scores64, int64_t* rows) {
+    nout = n;
+    os = out_scores = scores;
+    os64 = out_scores64 = scores64;
+    orr = out_rows = rows;
+    if (!host) return MRAG_OK;
     if (int rc = ensure(c->out_s, nout * 4)) return rc;
     if (int rc = ensure(c->out_r, nout * 8)) return rc;
     os = (float*)c->out_s.p;
@@ -2569,21 +2562,43 @@ int search_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k
       if (int rc = ensure(c->out_s64, nout * 8)) return rc;
       os64 = (double*)c->out_s64.p;
     }
+    return MRAG_OK;
   }
 
-  const Search q{ix, c, s, queries, host, nq, k, label_filter, label_filters, row_offset, os, os64, orr, profile};
+  // the end of the call's device work, waited for
+  int wait() {
+    if (int rc = wait_stream(c, s)) return rc;
+    drain.armed = false;
+    return MRAG_OK;
+  }
+
+  // a search's tail: the outputs copied back (host pointers), the wait, the stats published
+  int finish(const SearchStats& st) {
+    if (host) {
+      MRAG_HIP(hipMemcpyAsync(out_scores, os, nout * 4, hipMemcpyDeviceToHost, s));
+      MRAG_HIP(hipMemcpyAsync(out_rows, orr, nout * 8, hipMemcpyDeviceToHost, s));
+      if (out_scores64) MRAG_HIP(hipMemcpyAsync(out_scores64, os64, nout * 8, hipMemcpyDeviceToHost, s));
+    }
+    if (int rc = wait()) return rc;
+    publish_stats(ix, c, st);
+    return MRAG_OK;
+  }
+};
+
+// mrag_knn_search (label_filters null: label_filter for every query) and mrag_knn_search_labels.
+int search_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k, int32_t label_filter,
+                 const int32_t* label_filters, int64_t row_offset, float* out_scores, double* out_scores64,
+                 int64_t* out_rows, int32_t ptr_kind, void* stream_arg) {
+  SearchCall call(ix);
+  if (nq == 0) return MRAG_OK;
+  MRAG_REQUIRE(queries && out_scores && out_rows, "NULL query/output pointer");
+  if (int rc = call.open(ptr_kind, stream_arg)) return rc;
+  if (int rc = call.outputs(nq * k, out_scores, out_scores64, out_rows)) return rc;
+  const Search q{ix, call.c, call.s, queries, call.host, nq, k, label_filter, label_filters, row_offset, call.os,
+                 call.os64, call.orr, call.profile};
   SearchStats st;
   if (int rc = run_search(q, st)) return rc;
-
-  if (host) {
-    MRAG_HIP(hipMemcpyAsync(out_scores, os, nout * 4, hipMemcpyDeviceToHost, s));
-    MRAG_HIP(hipMemcpyAsync(out_rows, orr, nout * 8, hipMemcpyDeviceToHost, s));
-    if (out_scores64) MRAG_HIP(hipMemcpyAsync(out_scores64, os64, nout * 8, hipMemcpyDeviceToHost, s));
-  }
-  if (int rc = wait_stream(c, s)) return rc;
-  drain.armed = false;
-  publish_stats(ix, c, st);
-  return MRAG_OK;
+  return call.finish(st);
 }
 
 mrag_knn::MmrSelect mmr_args(const mrag_knn_index* ix, const int64_t* rows, const double* s64, int64_t nq, int m,
@@ -2611,36 +2626,12 @@ mrag_knn::MmrSelect mmr_args(const mrag_knn_index* ix, const int64_t* rows, cons
 int search_mmr_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32_t k, int32_t fetch_k, double lam,
                      int32_t label_filter, const int32_t* label_filters, int64_t row_offset, float* out_scores,
                      double* out_scores64, int64_t* out_rows, int32_t ptr_kind, void* stream_arg) {
-  std::shared_lock<std::shared_mutex> rl(ix->rw);
-  mrag::DeviceGuard g(ix->device);
-  SearchCtx* c = nullptr;
-  if (int rc = ctx_get(ix, &c)) return rc;
-  CtxLease lease{ix, c};
-  bool profile;
-  {
-    std::lock_guard<std::mutex> lk(ix->pool_mu);
-    profile = ix->profile;
-  }
-  hipStream_t s = stream_arg ? (hipStream_t)stream_arg : ix->stream;
-  const bool host = ptr_kind == MRAG_PTR_HOST;
-  if (!host && !stream_arg)
-    if (int rc = mrag::wait_null_stream(c->null_ev, s)) return rc;
-  mrag::StreamDrain drain(s);  // as in search_entry
+  SearchCall call(ix);
+  if (int rc = call.open(ptr_kind, stream_arg)) return rc;
+  if (int rc = call.outputs(nq * k, out_scores, out_scores64, out_rows)) return rc;
+  SearchCtx* c = call.c;
+  hipStream_t s = call.s;
   const int64_t nout = nq * k, ncand = nq * fetch_k;
-
-  float* os = out_scores;
-  double* os64 = out_scores64;
-  int64_t* orr = out_rows;
-  if (host) {
-    if (int rc = ensure(c->out_s, nout * 4)) return rc;
-    if (int rc = ensure(c->out_r, nout * 8)) return rc;
-    os = (float*)c->out_s.p;
-    orr = (int64_t*)c->out_r.p;
-    if (out_scores64) {
-      if (int rc = ensure(c->out_s64, nout * 8)) return rc;
-      os64 = (double*)c->out_s64.p;
-    }
-  }
   if (int rc = ensure(c->mmr_s, ncand * 4)) return rc;
   if (int rc = ensure(c->mmr_s64, ncand * 8)) return rc;
   if (int rc = ensure(c->mmr_r, ncand * 8)) return rc;
@@ -2651,8 +2642,8 @@ int search_mmr_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32
   int32_t* pos = (int32_t*)c->mmr_pos.p;
 
   // the candidates keep their local row ids: K16 reads the rows; the gather adds row_offset
-  const Search q{ix, c, s, queries, host, nq, fetch_k, label_filter, label_filters, 0, cand_s, cand_s64, cand_r,
-                 profile};
+  const Search q{ix, c, s, queries, call.host, nq, fetch_k, label_filter, label_filters, 0, cand_s, cand_s64, cand_r,
+                 call.profile};
   SearchStats st;
   if (int rc = run_search(q, st)) return rc;
   if (int rc = mrag_knn::mmr_select(mmr_args(ix, cand_r, cand_s64, nq, fetch_k, k, lam, pos, nullptr, nullptr), s))
@@ -2666,41 +2657,27 @@ int search_mmr_entry(mrag_knn_index* ix, const float* queries, int64_t nq, int32
   ga.m = fetch_k;
   ga.k = k;
   ga.row_offset = row_offset;
-  ga.out_s = os;
-  ga.out_s64 = os64;
-  ga.out_r = orr;
+  ga.out_s = call.os;
+  ga.out_s64 = call.os64;
+  ga.out_r = call.orr;
   if (int rc = mrag_knn::mmr_gather(ga, s)) return rc;
-
-  if (host) {
-    MRAG_HIP(hipMemcpyAsync(out_scores, os, nout * 4, hipMemcpyDeviceToHost, s));
-    MRAG_HIP(hipMemcpyAsync(out_rows, orr, nout * 8, hipMemcpyDeviceToHost, s));
-    if (out_scores64) MRAG_HIP(hipMemcpyAsync(out_scores64, os64, nout * 8, hipMemcpyDeviceToHost, s));
-  }
-  if (int rc = wait_stream(c, s)) return rc;
-  drain.armed = false;
-  publish_stats(ix, c, st);
-  return MRAG_OK;
+  return call.finish(st);
 }
 
 // mrag_knn_mmr_select: K16 on the caller's candidates.
 int mmr_select_entry(mrag_knn_index* ix, const int64_t* cand_rows, const double* cand_scores64, int64_t nq, int32_t m,
                      int32_t k, double lam, int32_t* out_pos, double* out_value64, int32_t ptr_kind,
                      void* stream_arg) {
-  std::shared_lock<std::shared_mutex> rl(ix->rw);
+  SearchCall call(ix);
   const bool host = ptr_kind == MRAG_PTR_HOST;
   const int64_t nout = nq * k, ncand = nq * m;
   if (host)  // a device array is checked by the kernel (below)
     for (int64_t i = 0; i < ncand; ++i)
       MRAG_REQUIRE(cand_rows[i] < ix->n, "cand_rows: row %lld of query %lld is not below the index size %lld",
                    (long long)cand_rows[i], (long long)(i / m), (long long)ix->n);
-  mrag::DeviceGuard g(ix->device);
-  SearchCtx* c = nullptr;
-  if (int rc = ctx_get(ix, &c)) return rc;
-  CtxLease lease{ix, c};
-  hipStream_t s = stream_arg ? (hipStream_t)stream_arg : ix->stream;
-  if (!host && !stream_arg)
-    if (int rc = mrag::wait_null_stream(c->null_ev, s)) return rc;
-  mrag::StreamDrain drain(s);
+  if (int rc = call.open(ptr_kind, stream_arg)) return rc;
+  SearchCtx* c = call.c;
+  hipStream_t s = call.s;
 
   const int64_t* rows = cand_rows;
   const double* s64 = cand_scores64;
@@ -2730,9 +2707,17 @@ int mmr_select_entry(mrag_knn_index* ix, const int64_t* cand_rows, const double*
     MRAG_HIP(hipMemcpyAsync(out_pos, pos, nout * 4, hipMemcpyDeviceToHost, s));
     if (out_value64) MRAG_HIP(hipMemcpyAsync(out_value64, val, nout * 8, hipMemcpyDeviceToHost, s));
   }
-  if (int rc = wait_stream(c, s)) return rc;
-  drain.armed = false;
+  if (int rc = call.wait()) return rc;
   MRAG_REQUIRE(c->host_counters[2] == 0, "cand_rows: a row id is not below the index size %lld", (long long)ix->n);
+  return MRAG_OK;
+}
+
+// Per-query filters in a host array are checked before any launch; a device array's entries
+// below MRAG_LABEL_ANY match nothing (mrag.h).
+int check_label_filters(const int32_t* label_filters, int64_t nq) {
+  for (int64_t i = 0; i < nq; ++i)
+    MRAG_REQUIRE(label_filters[i] >= MRAG_LABEL_ANY, "label filter %d of query %lld invalid", label_filters[i],
+                 (long long)i);
   return MRAG_OK;
 }
 
@@ -2935,12 +2920,8 @@ int mrag_knn_search_labels(mrag_knn_index* ix, const float* queries, int64_t nq,
   MRAG_REQUIRE(ptr_kind == MRAG_PTR_HOST || ptr_kind == MRAG_PTR_DEVICE, "bad ptr_kind %d", ptr_kind);
   MRAG_REQUIRE(nq < (1 << 24), "too many queries in one call");
   MRAG_REQUIRE(nq == 0 || label_filters != nullptr, "NULL label filters");
-  // a host array is checked here, before any launch; a device array's entries below
-  // MRAG_LABEL_ANY match nothing (mrag.h)
   if (ptr_kind == MRAG_PTR_HOST)
-    for (int64_t i = 0; i < nq; ++i)
-      MRAG_REQUIRE(label_filters[i] >= MRAG_LABEL_ANY, "label filter %d of query %lld invalid", label_filters[i],
-                   (long long)i);
+    if (int rc = check_label_filters(label_filters, nq)) return rc;
   return search_entry(ix, queries, nq, k, MRAG_LABEL_ANY, label_filters, row_offset, out_scores, out_scores64,
                       out_rows, ptr_kind, stream_arg);
 }
@@ -2957,10 +2938,8 @@ int mrag_knn_search_mmr(mrag_knn_index* ix, const float* queries, int64_t nq, in
   MRAG_REQUIRE(out_scores != nullptr, "out_scores is NULL");
   MRAG_REQUIRE(out_rows != nullptr, "out_rows is NULL");
   if (label_filters) {
-    if (ptr_kind == MRAG_PTR_HOST)  // as mrag_knn_search_labels
-      for (int64_t i = 0; i < nq; ++i)
-        MRAG_REQUIRE(label_filters[i] >= MRAG_LABEL_ANY, "label filter %d of query %lld invalid", label_filters[i],
-                     (long long)i);
+    if (ptr_kind == MRAG_PTR_HOST)
+      if (int rc = check_label_filters(label_filters, nq)) return rc;
   } else {
     MRAG_REQUIRE(label_filter >= MRAG_LABEL_ANY, "label filter %d invalid", label_filter);
   }

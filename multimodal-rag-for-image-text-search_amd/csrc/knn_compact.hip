@@ -13,6 +13,7 @@
 // Both are memory-bound: K15a moves 12 bytes per row (labels twice, remap once), K15b reads and
 // writes 6 DP + 12 bytes per live row.
 #include "knn_compact.h"
+#include "devbuf.h"
 
 #include <algorithm>
 
@@ -226,14 +227,14 @@ extern "C" int mrag_knn_row_remap(const int32_t* labels, int64_t n, int32_t* rem
   MRAG_REQUIRE(labels != nullptr && remap != nullptr, "NULL labels/remap");
   MRAG_REQUIRE(((uintptr_t)labels & 15) == 0 && ((uintptr_t)remap & 15) == 0, "labels and remap must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  int32_t* scratch = nullptr;  // [0]: the live count; from word 4: the block sums
-  MRAG_HIP(hipMalloc((void**)&scratch, mrag_knn::remap_scratch_words(n) * 4));
+  mrag::DevBuf buf;  // exactly these bytes (a fresh buffer); freed on every path, after the wait below
+  if (int rc = mrag::ensure_doubling(buf, mrag_knn::remap_scratch_words(n) * 4)) return rc;
+  int32_t* scratch = (int32_t*)buf.p;  // [0]: the live count; from word 4: the block sums
   int rc = mrag_knn::row_remap(labels, n, remap, scratch, scratch + 4, s);
   int32_t got = 0;
   hipError_t e = hipSuccess;
   if (rc == MRAG_OK) e = hipMemcpyAsync(&got, scratch, 4, hipMemcpyDeviceToHost, s);
   const hipError_t e2 = hipStreamSynchronize(s);  // before the scratch is freed, on every path
-  (void)hipFree(scratch);
   if (rc != MRAG_OK) return rc;
   MRAG_HIP(e);
   MRAG_HIP(e2);

@@ -6,16 +6,12 @@
 #pragma once
 
 #include "common.h"
+#include "devbuf.h"
 
 namespace mrag_knn {
 
 constexpr int GENERIC_MAX_DIM = 4096;
 constexpr int GENERIC_MAX_K = 65536;
-
-struct Workspace {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
 
 struct GenericSearch {
   // corpus (the index's buffers): rows padded to DP, labels padded to a multiple of 256
@@ -73,10 +69,8 @@ __device__ __forceinline__ double exact_cosine16(const float* qs, double qn, con
 // Two GEMM passes over the corpus (score histogram -> per-query collect threshold ->
 // candidate collection -> exact f64 rescoring + ordered selection). Exact for every input;
 // the per-query candidate storage is sized from the histogram (never by a global cap).
-// `ws` holds 8 reusable device buffers; *n_candidates (optional) receives the total number
-// of rows rescored exactly.
-int search_generic(const GenericSearch& a, Workspace (&ws)[8], hipStream_t s, int64_t* n_candidates);
-
-void release(Workspace (&ws)[8]);
+// `ws` holds 8 reusable device buffers (the caller's: freed with it); *n_candidates (optional)
+// receives the total number of rows rescored exactly.
+int search_generic(const GenericSearch& a, mrag::DevBuf (&ws)[8], hipStream_t s, int64_t* n_candidates);
 
 }  // namespace mrag_knn

@@ -294,19 +294,6 @@ __global__ __launch_bounds__(GF_THREADS) void generic_final_kernel(FinalParams p
   }
 }
 
-int ensure(Workspace& b, size_t bytes) {
-  if (b.bytes >= bytes && b.p) return MRAG_OK;
-  if (b.p) {
-    MRAG_HIP(hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  const size_t want = std::max<size_t>(bytes, 256);
-  MRAG_HIP(hipMalloc(&b.p, want));
-  b.bytes = want;
-  return MRAG_OK;
-}
-
 int gemm_scores(const GenericSearch& a, int q_lo, int mq, int64_t r0, int ncols, float* S, hipStream_t s) {
   mrag_enc::GemmArgs g{};
   g.A = a.q16 + (size_t)q_lo * a.DP;
@@ -331,15 +318,7 @@ double eps_for_dim(int D) {
   return std::max(1.05e-3, e * 1.02);
 }
 
-void release(Workspace (&ws)[8]) {
-  for (auto& w : ws) {
-    if (w.p) (void)hipFree(w.p);
-    w.p = nullptr;
-    w.bytes = 0;
-  }
-}
-
-int search_generic(const GenericSearch& a, Workspace (&ws)[8], hipStream_t s, int64_t* n_candidates) {
+int search_generic(const GenericSearch& a, mrag::DevBuf (&ws)[8], hipStream_t s, int64_t* n_candidates) {
   MRAG_REQUIRE(a.DP % 128 == 0 && a.DP <= GENERIC_MAX_DIM && a.D <= a.DP, "K7g: dim %d unsupported", a.D);
   MRAG_REQUIRE(a.k >= 1 && a.k <= GENERIC_MAX_K, "K7g: k=%d unsupported (1..%d)", a.k, GENERIC_MAX_K);
   if (n_candidates) *n_candidates = 0;

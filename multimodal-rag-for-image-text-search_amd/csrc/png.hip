@@ -26,6 +26,8 @@
 #include <vector>
 
 #include "common.h"
+#include "devbuf.h"
+#include "host_threads.h"
 #include "png_parse.h"
 #include "staged.h"
 
@@ -151,29 +153,13 @@ __global__ __launch_bounds__(64 * PNG_WAVES) void png_unfilter_kernel(const PngI
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-int ensure(DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return MRAG_OK;
-  const size_t c = std::max(bytes, b.cap * 2);
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  MRAG_HIP(hipMalloc(&b.p, c));
-  b.cap = c;
-  return MRAG_OK;
-}
-
 // Per-device scratch, grown on demand and reused by every batch (calls serialise on its lock).
 struct Ctx {
   std::mutex mu;
-  DevBuf raw, imgs;
-  uint8_t* stage = nullptr;  // pinned host staging of the filtered scanlines
-  size_t stage_cap = 0;
+  mrag::DevBuf raw, imgs;
+  mrag::PinnedBuf stage;  // host staging of the filtered scanlines
 };
-Ctx g_ctx[64];
+Ctx* const g_ctx = new Ctx[64];  // never deleted: no hipFree at process exit, when the HIP runtime may be gone
 
 }  // namespace
 
@@ -231,35 +217,26 @@ static int png_unfilter_impl(const uint8_t* const* raws, const int32_t* dims, in
   Ctx& C = g_ctx[device];
   std::lock_guard<std::mutex> lk(C.mu);
   hipStream_t s = (hipStream_t)stream;
-  if (!staged && total > (int64_t)C.stage_cap) {
-    const size_t cap = std::max<size_t>((size_t)total, C.stage_cap * 2);
-    if (int rc = mrag::blocking_wait(s)) return rc;
-    if (C.stage) (void)hipHostFree(C.stage);
-    C.stage = nullptr;
-    C.stage_cap = 0;
-    MRAG_HIP(hipHostMalloc((void**)&C.stage, cap, hipHostMallocDefault));
-    C.stage_cap = cap;
+  if (!staged && total > (int64_t)C.stage.bytes) {
+    if (int rc = mrag::blocking_wait(s)) return rc;  // a previous batch's copy may still read the old buffer
+    if (int rc = mrag::ensure_doubling(C.stage, (size_t)total)) return rc;
   }
   if (!staged) {
     if (int rc = mrag::blocking_wait(s)) return rc;  // the previous batch's copy out of the stage is done
     const int nth =
         (int)std::max<int64_t>(1, std::min<int64_t>({8, (int64_t)std::thread::hardware_concurrency(), (n + 3) / 4}));
-    std::vector<std::thread> th;
-    auto copy = [&](int w0) {
-      for (int i = w0; i < n; i += nth)
-        std::memcpy(C.stage + imgs[i].raw_off, raws[i],
-                    (size_t)((int64_t)imgs[i].h * (1 + (int64_t)imgs[i].w * imgs[i].bpp)));
-    };
-    for (int w0 = 1; w0 < nth; ++w0) th.emplace_back(copy, w0);
-    copy(0);
-    for (auto& t : th) t.join();
+    const bool copied = mrag::for_each_index(n, nth, [&](int i) {
+      std::memcpy(C.stage.p + imgs[i].raw_off, raws[i],
+                  (size_t)((int64_t)imgs[i].h * (1 + (int64_t)imgs[i].w * imgs[i].bpp)));
+    });
+    if (!copied) return mrag::fail(MRAG_ERR_OOM, "png: host allocation failed while staging");
   }
-  if (int rc = ensure(C.raw, (size_t)total)) return rc;
-  if (int rc = ensure(C.imgs, sizeof(PngImg) * (size_t)n)) return rc;
+  if (int rc = mrag::ensure_doubling(C.raw, (size_t)total)) return rc;
+  if (int rc = mrag::ensure_doubling(C.imgs, sizeof(PngImg) * (size_t)n)) return rc;
   // an error return from here on first drains s: the copies read imgs on this stack frame and the
   // staging buffer, which the caller may hand back to its pool
   mrag::StreamDrain drain(s);
-  MRAG_HIP(hipMemcpyAsync(C.raw.p, staged ? staged : C.stage, (size_t)total, hipMemcpyHostToDevice, s));
+  MRAG_HIP(hipMemcpyAsync(C.raw.p, staged ? staged : C.stage.p, (size_t)total, hipMemcpyHostToDevice, s));
   MRAG_HIP(hipMemcpyAsync(C.imgs.p, imgs.data(), sizeof(PngImg) * (size_t)n, hipMemcpyHostToDevice, s));
   // one launch per pixel size present (a workgroup of another size returns at once)
   bool has[5] = {false, false, false, false, false};

@@ -4,15 +4,13 @@
 // lowercasing maps A-Z only, `\w` is [0-9A-Za-z_] and `\s` is Python's str whitespace (\t \n \v \f
 // \r, space, \x1c-\x1f): the same tokens and the same zlib crc32 as the Python path, without the
 // interpreter, on this library's threads. Texts with a non-ASCII byte are left to the caller.
-#include <atomic>
 #include <cstdint>
 #include <cstring>
-#include <thread>
-#include <vector>
 
 #include <zlib.h>
 
 #include "common.h"
+#include "host_threads.h"
 
 namespace {
 
@@ -43,47 +41,35 @@ extern "C" int mrag_hash_tokenize(const char* const* texts, const int64_t* lens,
   MRAG_REQUIRE(n >= 0 && (n == 0 || (texts && lens && ids && counts)), "NULL argument");
   MRAG_REQUIRE(hi > lo && lo >= 0 && max_tokens > 0, "tokenize: bad id range or max_tokens");
   const uint32_t span = (uint32_t)(hi - lo);
-  std::atomic<int> next{0};
-  auto work = [&]() {
-    for (int i = next++; i < n; i = next++) {
-      const unsigned char* s = (const unsigned char*)texts[i];
-      const int64_t L = lens[i];
-      int32_t* out = ids + (size_t)i * (size_t)max_tokens;
-      int32_t c = 0;
-      bool ascii = true;
-      for (int64_t k = 0; k < L; ++k)
-        if (s[k] >= 0x80) {
-          ascii = false;
-          break;
-        }
-      if (!ascii) {
-        counts[i] = -1;
+  (void)mrag::for_each_index(n, threads, [&](int i) {  // the body does not throw
+    const unsigned char* s = (const unsigned char*)texts[i];
+    const int64_t L = lens[i];
+    int32_t* out = ids + (size_t)i * (size_t)max_tokens;
+    int32_t c = 0;
+    bool ascii = true;
+    for (int64_t k = 0; k < L; ++k)
+      if (s[k] >= 0x80) {
+        ascii = false;
+        break;
+      }
+    if (!ascii) {
+      counts[i] = -1;
+      return;
+    }
+    int64_t k = 0;
+    while (k < L && c < max_tokens) {
+      const unsigned char ch = s[k];
+      if (is_space(ch)) {
+        ++k;
         continue;
       }
-      int64_t k = 0;
-      while (k < L && c < max_tokens) {
-        const unsigned char ch = s[k];
-        if (is_space(ch)) {
-          ++k;
-          continue;
-        }
-        int64_t e = k + 1;
-        if (is_word(ch))
-          while (e < L && is_word(s[e])) ++e;
-        out[c++] = lo + (int32_t)(crc_lower(s + k, e - k) % span);
-        k = e;
-      }
-      counts[i] = c;
+      int64_t e = k + 1;
+      if (is_word(ch))
+        while (e < L && is_word(s[e])) ++e;
+      out[c++] = lo + (int32_t)(crc_lower(s + k, e - k) % span);
+      k = e;
     }
-  };
-  const int nth = threads > 1 ? (threads < n ? threads : n) : 1;
-  std::vector<std::thread> th;
-  try {
-    th.reserve((size_t)nth);
-    for (int t = 1; t < nth; ++t) th.emplace_back(work);
-  } catch (...) {  // fewer helpers than asked: this thread and the started ones finish the work
-  }
-  work();
-  for (auto& x : th) x.join();
+    counts[i] = c;
+  });
   return MRAG_OK;
 }

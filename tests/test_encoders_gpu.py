@@ -451,3 +451,20 @@ def test_small_batch_graph_replay_bit_identical(cuda, tower):
     for b, n in [(1, 5), (1, 12)]:  # the old graphs baked the freed buffers: recaptured
         h, d = both(*query(b, n))
         np.testing.assert_array_equal(h, d, err_msg=f"after growth B={b} T={n}")
+
+
+def test_workspace_per_sequence_buffers_grow_alone(cuda):
+    """The workspace's per-sequence buffers grow with B, its per-token ones with B * T: after
+    (B, T) = (2, 16), a batch of (4, 8) has as many tokens and twice the sequences, so only the
+    per-sequence buffers are made again. Each result on the one handle == the same batch on a
+    fresh handle, bit for bit."""
+    from app.encoders import MINILM_L6, GpuEncoder
+
+    rng = np.random.default_rng(29)
+    enc = GpuEncoder(MINILM_L6)
+    for b, n in [(2, 16), (4, 8)]:
+        ids = rng.integers(1000, 30000, (b, n)).astype(np.int32)
+        ids[:, 0], ids[:, -1] = 101, 102
+        mask = np.ones_like(ids)
+        got = enc.embed_tokens(ids, mask)
+        np.testing.assert_array_equal(got, GpuEncoder(MINILM_L6).embed_tokens(ids, mask), err_msg=f"B={b} T={n}")
